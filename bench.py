@@ -9,10 +9,25 @@ tiles with one RCCL gather over xGMI (rtow_dist.py).  Strong scaling: the frame 
 split it.  `value` = closest-hit queries (ray segments) of all ranks per
 second of the max-over-ranks wall time / 1e6.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
-Extra objects on the JSON line:
+A plain run does what the headline figure needs and no more: it sets up, loads
+the kernels on a tiny frame, renders the warmup frames, times the K steps,
+writes the last step's outputs if --dump-outputs is given, and prints the JSON
+line.  `ms_per_step` is the wall time of the timed region / K.
+
+--dump-outputs DIR writes what the last timed step computed (seed K - 1, so
+equal arguments give equal frames) as float32 .npy files:
+  pixel_sums.npy   rank 0's fp32 radiance sums, [pixels, 3] (rt_render_async)
+  frame_bytes.npy  the assembled frame's write_color bytes, [pixels, 3]
+Arrays too large for the dump's size budget are cut to a fixed, seeded sample
+of their pixels (the same pixels in every run of the same frame size).
+
+--full adds, after the timed region: the check of the device write_color
+against the host's, and the objects below on the JSON line:
+  work_per_launch_rank0  executed work of one launch, from one extra frame of
+               the work-counting kernel build (RT_FLAG_COUNT_WORK)
   roofline     fp32 VALU roofline of the render kernel: executed flops (ray-sphere
                tests x 17 + grid cell steps x 2, counted in-kernel) per launch /
                average launch time from HIP events on the launch stream, against
@@ -81,11 +96,19 @@ def parse():
     ap.add_argument("--cpu-spp", type=int, default=10, help="spp of the bounded CPU sample (400x225: C0)")
     ap.add_argument("--cpu-procs", type=int, default=0,
                     help="concurrent reference processes for the all-cores figure (0: min(16, cpu count))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out (a plain run never measures it)")
     ap.add_argument("--no-pilot", action="store_true",
                     help="launch tiles in index order (no RT_FLAG_PILOT_SCHEDULE)")
     ap.add_argument("--out", default="", help="write the gathered frame as PPM (P6 if .pgm/.p6)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the bytes against the host write_color and add the work counts, "
+                         "the roofline and the CPU baseline to the JSON line")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.preset:
         a.width, a.height, a.spp, a.half_extent = PRESETS[a.preset]
     return a
@@ -129,6 +152,27 @@ def cpu_baseline(spp, procs):
     dt = time.perf_counter() - t
     return {"value": round(segs / dt / 1e6, 4), "unit": "Mray/s", "cores": 1, "kind": "port",
             "seconds": round(dt, 3), "sample": sample + ", single thread (oracle fp64 restatement)"}
+
+
+DUMP_BUDGET_BYTES = 48_000_000  # all dumped arrays together (float32), inside the 64 MB a dump may take
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(path, arrays):
+    """Write each [pixels, 3] array of `arrays` as path/<name>.npy in float32.
+    The arrays share DUMP_BUDGET_BYTES equally; one that is larger than its
+    share is cut to a sample of its pixels, drawn without replacement by a
+    generator seeded with DUMP_SAMPLE_SEED and kept in pixel order, so two runs
+    on the same frame size dump the same pixels."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    keep = DUMP_BUDGET_BYTES // (len(arrays) * 3 * 4)
+    for name, arr in arrays.items():
+        arr = arr.reshape(-1, 3)
+        if arr.shape[0] > keep:
+            idx = np.random.default_rng(DUMP_SAMPLE_SEED).choice(arr.shape[0], keep, replace=False)
+            arr = arr[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def load_pmc(workload, accel="scan", world=1):
@@ -329,22 +373,27 @@ def main():
         torch.cuda.synchronize(dev)
         barrier()
         elapsed = time.perf_counter() - t0
-    # the last timed frame's sums and bytes (the work frame below reuses the tile)
-    sums_last, u8_last = tile.cpu().numpy(), tile_u8.cpu().numpy()
+    # the last timed frame's sums and bytes (the work frame below reuses the tile),
+    # copied back only for what reads them: the dump, the PPM, the --full check
+    sums_last = u8_last = None
+    if rank == 0 and (a.full or a.out or a.dump_outputs):
+        sums_last, u8_last = tile.cpu().numpy(), tile_u8.cpu().numpy()
 
     st = ctx.collect_stats()
     kernel_ms = [e[0].elapsed_time(e[1]) for e in evs]
     tonemap_ms = [e[1].elapsed_time(e[2]) for e in evs]
     gather_ms = [e[2].elapsed_time(e[3]) for e in evs]
-    # executed work per launch: one instrumented frame (RT_FLAG_COUNT_WORK build),
-    # same seed as timed step 0, outside the timed region
-    wp = rtow_dist.partition(W, H, spp, world, rank, a.row_block, max_depth=a.depth,
-                             flags=(params.flags & ~rtow.RT_FLAG_KEEP_COUNTERS) | rtow.RT_FLAG_COUNT_WORK)
-    wp.seed = 0
-    with torch.cuda.stream(stream):
-        ctx.render_async(cam, wp, tile.data_ptr(), stream.cuda_stream)
-        torch.cuda.synchronize(dev)
-    work = ctx.collect_stats()
+    work = None
+    if a.full:
+        # executed work per launch: one instrumented frame (RT_FLAG_COUNT_WORK build),
+        # same seed as timed step 0, outside the timed region
+        wp = rtow_dist.partition(W, H, spp, world, rank, a.row_block, max_depth=a.depth,
+                                 flags=(params.flags & ~rtow.RT_FLAG_KEEP_COUNTERS) | rtow.RT_FLAG_COUNT_WORK)
+        wp.seed = 0
+        with torch.cuda.stream(stream):
+            ctx.render_async(cam, wp, tile.data_ptr(), stream.cuda_stream)
+            torch.cuda.synchronize(dev)
+        work = ctx.collect_stats()
     local = torch.tensor([float(st.segments), float(st.samples), float(st.wave_steps)],
                          dtype=torch.float64, device=gdev)
     mean = lambda v: sum(v) / len(v)
@@ -358,22 +407,24 @@ def main():
     elapsed, render_ms_max, tonemap_ms_max, gather_ms_max = t_max.tolist()
 
     if rank == 0:
-        # assemble the last frame on rank 0 (outside the timed region) and sanity-check it
-        if world > 1:
-            tiles = torch.stack(gather_list).cpu().numpy()
-        else:
-            tiles = u8_last[None]
-        frame = rtow_dist.assemble(tiles, H, world, a.row_block)
-        assert np.isfinite(sums_last).all() and sums_last.max() <= spp + 1e-3
-        assert np.array_equal(u8_last, rtow.tonemap(sums_last, max(spp, 1)))
-        if a.out:
-            rtow.write_ppm(a.out, frame, binary=a.out.endswith((".p6", ".pnm")))
+        if a.out or a.dump_outputs:
+            # assemble the last frame on rank 0 (outside the timed region)
+            if world > 1:
+                tiles = torch.stack(gather_list).cpu().numpy()
+            else:
+                tiles = u8_last[None]
+            frame = rtow_dist.assemble(tiles, H, world, a.row_block)
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, {"pixel_sums": sums_last, "frame_bytes": frame})
+            if a.out:
+                rtow.write_ppm(a.out, frame, binary=a.out.endswith((".p6", ".pnm")))
+        if a.full:
+            # sanity-check the last frame: finite sums, device write_color == the host's
+            assert np.isfinite(sums_last).all() and sums_last.max() <= spp + 1e-3
+            assert np.array_equal(u8_last, rtow.tonemap(sums_last, max(spp, 1)))
 
         k_avg_s = sum(kernel_ms) / len(kernel_ms) / 1e3
         value = segments / elapsed / 1e6
-        pmc, pmc_reason = load_pmc(workload, a.accel, world)
-        roof = roofline({"sphere_tests": work.sphere_tests, "box_tests": work.box_tests,
-                         "bf_tests": work.bf_tests}, k_avg_s, a.accel, pmc, pmc_reason, rtow.device_code_sha16())
         out = {
             "metric": "Mray/s (ray segments = closest-hit queries per second), final random-spheres "
                       "scene 3840x2160 @ 500spp depth 50" if not a.preset or a.preset == "c2"
@@ -408,9 +459,6 @@ def main():
                      "layer_bvh": "wave-uniform layer BVH + extras scanned"}[a.accel],
             "schedule": "launch order" if a.no_pilot else
                         "pilot (expensive tiles first; 4-spp pilot in the warmup frame)",
-            "work_per_launch_rank0": {"segments": work.segments, "sphere_tests": work.sphere_tests,
-                                      "box_tests": work.box_tests, "box_hits_own_ray": work.box_hits,
-                                      "brute_force_equiv_tests": work.bf_tests},
             "first_frame_ms": round(first_frame_ms, 3) if first_frame_ms is not None else None,
             "first_frame_note": "wall time of the first frame of this geometry on its own, pilot schedule "
                                 "included (4-spp pilot + device sort of the tile order); ms_per_step "
@@ -421,20 +469,28 @@ def main():
                               "basis": "HIP events on each rank's launch stream around its render, "
                                        "its device write_color and the RCCL gather of the byte tiles "
                                        "(0 at N = 1); mean over the timed steps, max over ranks"},
-            "roofline": roof,
-            "cpu_baseline": None,
-            "cpu_baseline_note": None if world == 1 else
-                                 "measured at N = 1 only (rank 0's host cores would be shared with "
-                                 "N render processes); see the N = 1 line",
+            "full": a.full,
         }
-        if world == 1 and a.no_cpu_baseline:
-            out["cpu_baseline_note"] = "skipped (--no-cpu-baseline)"
-        if world == 1 and not a.no_cpu_baseline:
-            try:
-                procs = a.cpu_procs or min(16, os.cpu_count() or 1)
-                out["cpu_baseline"] = cpu_baseline(a.cpu_spp, procs)
-            except Exception as e:  # the GPU number stands on its own
-                out["cpu_baseline"] = {"value": None, "error": repr(e)[:200]}
+        if a.full:
+            pmc, pmc_reason = load_pmc(workload, a.accel, world)
+            out["work_per_launch_rank0"] = {"segments": work.segments, "sphere_tests": work.sphere_tests,
+                                            "box_tests": work.box_tests, "box_hits_own_ray": work.box_hits,
+                                            "brute_force_equiv_tests": work.bf_tests}
+            out["roofline"] = roofline({"sphere_tests": work.sphere_tests, "box_tests": work.box_tests,
+                                        "bf_tests": work.bf_tests}, k_avg_s, a.accel, pmc, pmc_reason,
+                                       rtow.device_code_sha16())
+            out["cpu_baseline"] = None
+            out["cpu_baseline_note"] = (None if world == 1 else
+                                        "measured at N = 1 only (rank 0's host cores would be shared with "
+                                        "N render processes); see the N = 1 line")
+            if world == 1 and a.no_cpu_baseline:
+                out["cpu_baseline_note"] = "skipped (--no-cpu-baseline)"
+            if world == 1 and not a.no_cpu_baseline:
+                try:
+                    procs = a.cpu_procs or min(16, os.cpu_count() or 1)
+                    out["cpu_baseline"] = cpu_baseline(a.cpu_spp, procs)
+                except Exception as e:  # the GPU number stands on its own
+                    out["cpu_baseline"] = {"value": None, "error": repr(e)[:200]}
         print(json.dumps(out), flush=True)
     ctx.close()
     if world > 1:

@@ -90,6 +90,32 @@ def test_counters_of_other_device_code_are_nulled():
         assert 0 < roof["frac"] <= 1  # from the live HIP-event time and the work counters
 
 
+def test_dump_outputs_whole_when_small_and_a_fixed_sample_when_large(tmp_path, monkeypatch):
+    """--dump-outputs: float32 [pixels, 3] files; an array inside its share of
+    the budget is written whole, a larger one as the same seeded sample of
+    its pixels, in pixel order, on every call."""
+    import numpy as np
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 1000 * 1000
+    rng = np.random.default_rng(1)
+    sums = rng.random((9, 7, 3)).astype(np.float32)
+    u8 = rng.integers(0, 256, (9, 7, 3)).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), {"pixel_sums": sums, "frame_bytes": u8})
+    got = np.load(tmp_path / "a" / "frame_bytes.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, u8.reshape(-1, 3))
+    assert np.array_equal(np.load(tmp_path / "a" / "pixel_sums.npy"), sums.reshape(-1, 3))
+    # a budget of 20 pixels per array: 63 pixels are cut to 20 of them
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 20 * 12)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"pixel_sums": sums, "frame_bytes": u8})
+    b, c = np.load(tmp_path / "b" / "pixel_sums.npy"), np.load(tmp_path / "c" / "pixel_sums.npy")
+    assert b.shape == (20, 3) and np.array_equal(b, c)
+    flat = sums.reshape(-1, 3)
+    rows = [int(np.flatnonzero((flat == p).all(axis=1))[0]) for p in b]
+    assert rows == sorted(set(rows))
+    bytes_b = np.load(tmp_path / "b" / "frame_bytes.npy")
+    assert np.array_equal(bytes_b, u8.reshape(-1, 3)[rows])  # the same pixels in both arrays
+
+
 def test_committed_summaries_carry_the_built_device_code(rtow):
     """Every committed pmc_traffic_bvh*.json (the N = 1, 2, 4, 8 lines' counter
     sources) was collected on the kernel this tree builds: the sha256 of the

@@ -95,7 +95,7 @@ def test_bench_two_ranks_gloo_traces_the_same_frames(tmp_path):
     identical segment totals, both ranks' work counted, and the byte tiles
     gathered and assembled on rank 0 give the same image, byte for byte."""
     common = ["--steps", "2", "--warmup", "1", "--width", "256", "--height", "144", "--spp", "16",
-              "--no-cpu-baseline"]
+              "--full", "--no-cpu-baseline"]
     one = _bench(common + ["--out", str(tmp_path / "one.ppm")])
     two = _bench(common + ["--gpus", "2", "--backend", "gloo", "--out", str(tmp_path / "two.ppm")], nproc=2)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2

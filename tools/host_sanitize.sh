@@ -7,8 +7,10 @@
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 PKG=$ROOT/ray-tracing-in-one-weekend_amd
-OUT=${TMPDIR:-/tmp}/rtow_host_sanitize
-mkdir -p $OUT
+# a private directory per run (a fixed name would be shared with other users'
+# runs, and unwritable after theirs), removed on exit
+OUT=$(mktemp -d "${TMPDIR:-/tmp}/rtow_host_sanitize.XXXXXX")
+trap 'rm -rf "$OUT"' EXIT
 HSAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined"
 FLAGS="--offload-arch=gfx950 -std=c++17 -fPIC -g -O1 -fno-omit-frame-pointer -I$ROOT/include -I$PKG/csrc"
 HIPCC=/opt/rocm/bin/hipcc
