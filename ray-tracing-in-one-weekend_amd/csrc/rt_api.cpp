@@ -20,6 +20,7 @@
 
 #include "rt_internal.h"
 #include "rt_accel.h"
+#include "rt_frame.h"
 #include "rt_layout.h"
 
 extern "C" void rt_internal_set_hip_error(int e);
@@ -558,32 +559,24 @@ launch_plan plan_launches(const rt_params *prm, double launch_samples) {
   return launch_plan{units, ranges, chunks, entries};
 }
 
-int render_enqueue_body(rt_context *c, const rt_camera *cam, const rt_params *prm, float *accum_rgb, hipStream_t st,
-                        hipEvent_t ev_start) {
+// What every pass over the context's scene does before its launches
+// (rt_internal_frame_begin: the render below and librtow_aov.so's first-hit
+// pass): the device, the wait on the context's previous pass, the kernel
+// arguments and the layer grid's refit for this frame geometry.
+int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipStream_t st, rt_frame_setup &fs) {
+  std::memset(&fs, 0, sizeof fs);
+  fs.stream = st;
+  fs.placement = rtk::kGridGlobal;
+  fs.launch_samples = c->launch_samples;
+  fs.ev0 = c->ev0;
+  fs.ev1 = c->ev1;
   RT_HIP(hipSetDevice(c->device));
-  // renders of one context are serialised, whatever streams they come on:
-  // they share the block-order scratch buffer
+  // passes of one context are serialised, whatever streams they come on:
+  // they share the block-order scratch buffer and the grid's buffers
   if (c->have_done && c->last_stream != st) RT_HIP(hipStreamWaitEvent(st, c->ev_done, 0));
-  const uint64_t samples = (uint64_t)prm->width * valid_rows(prm) * (uint64_t)prm->spp;
-  if (prm->flags & RT_FLAG_KEEP_COUNTERS) {
-    c->last_samples += samples;
-  } else {
-    RT_HIP(hipMemsetAsync(c->d_counters, 0, 8 * rtk::kCounterSlots * sizeof(unsigned long long), st));
-    c->last_samples = samples;
-    c->last_launches = 0;
-  }
-  c->last_stats = (prm->flags & RT_FLAG_COUNT_WORK) != 0;
-  c->enq_launches = 0;
-  if (prm->width == 0 || prm->local_rows == 0) {
-    if (ev_start) RT_HIP(hipEventRecord(ev_start, st));
-    return RT_OK;
-  }
-
-  rtk::kparams kp;
-  fill_kparams(c, cam, prm, accum_rgb, kp);
-  const int tiles_y = (prm->local_rows + rtk::kTile - 1) / rtk::kTile;
-  const long long tiles = (long long)kp.tiles_x * tiles_y;
-  const unsigned blocks = (unsigned)((tiles + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock);
+  if (prm->width == 0 || prm->local_rows == 0) return RT_OK;  // nothing to launch
+  rtk::kparams &kp = fs.kp;
+  fill_kparams(c, cam, prm, nullptr, kp);
   const bool grid = c->d_grid_cells && !(prm->flags & RT_FLAG_LAYER_BVH);
   if (grid && c->fitter && (prm->flags & RT_FLAG_ACCEL_BVH)) {
     // the layer grid's cell size for this frame geometry (rtk::grid_fitter:
@@ -647,10 +640,50 @@ int render_enqueue_body(rt_context *c, const rt_camera *cam, const rt_params *pr
       c->fit_key = key;
     }
   }
-  const int place = grid ? c->grid_placement : rtk::kGridGlobal;
+  fs.grid = grid ? 1 : 0;
+  fs.placement = grid ? c->grid_placement : rtk::kGridGlobal;
+  fs.lds_bytes = rtk::grid_lds_bytes(fs.placement, kp.grid_n_items, kp.grid_n_cells);
+  return RT_OK;
+}
+
+// ... and after them: ev_done on the pass's stream (rt_internal_frame_end)
+int frame_end(rt_context *c, hipStream_t st) {
+  RT_HIP(hipEventRecord(c->ev_done, st));
+  c->last_stream = st;
+  c->have_done = true;
+  return RT_OK;
+}
+
+int render_enqueue_body(rt_context *c, const rt_camera *cam, const rt_params *prm, float *accum_rgb, hipStream_t st,
+                        hipEvent_t ev_start) {
+  rt_frame_setup fs;
+  {
+    const int r = frame_begin(c, cam, prm, st, fs);
+    if (r != RT_OK) return r;
+  }
+  const uint64_t samples = (uint64_t)prm->width * valid_rows(prm) * (uint64_t)prm->spp;
+  if (prm->flags & RT_FLAG_KEEP_COUNTERS) {
+    c->last_samples += samples;
+  } else {
+    RT_HIP(hipMemsetAsync(c->d_counters, 0, 8 * rtk::kCounterSlots * sizeof(unsigned long long), st));
+    c->last_samples = samples;
+    c->last_launches = 0;
+  }
+  c->last_stats = (prm->flags & RT_FLAG_COUNT_WORK) != 0;
+  c->enq_launches = 0;
+  if (prm->width == 0 || prm->local_rows == 0) {
+    if (ev_start) RT_HIP(hipEventRecord(ev_start, st));
+    return RT_OK;
+  }
+
+  rtk::kparams &kp = fs.kp;
+  kp.out = accum_rgb;
+  const int tiles_y = (prm->local_rows + rtk::kTile - 1) / rtk::kTile;
+  const long long tiles = (long long)kp.tiles_x * tiles_y;
+  const unsigned blocks = (unsigned)((tiles + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock);
   const sum_fmt fmt = sum_format(prm->spp, prm->max_depth, c->max_albedo);
   const int v = render_variant(c, prm, fmt.wide);
-  const size_t lds = rtk::grid_lds_bytes(place, kp.grid_n_items, kp.grid_n_cells);
+  const size_t lds = fs.lds_bytes;
   const bool traced = prm->spp > 0 && prm->max_depth > 0;
   const launch_plan lp = plan_launches(prm, c->launch_samples);
   const long long units = lp.units, ranges = lp.ranges, chunks = lp.chunks, entries = lp.entries;
@@ -763,10 +796,7 @@ int render_enqueue_body(rt_context *c, const rt_camera *cam, const rt_params *pr
     RT_HIP(rtk::launch_finish_sums_wide(c->d_wide, accum_rgb, frame_floats, kp.qinv, st));
   else if (kp.sum_atomic)
     RT_HIP(rtk::launch_finish_sums(reinterpret_cast<uint32_t *>(accum_rgb), frame_floats, kp.qinv, st));
-  RT_HIP(hipEventRecord(c->ev_done, st));
-  c->last_stream = st;
-  c->have_done = true;
-  return RT_OK;
+  return frame_end(c, st);
 }
 
 // A render that fails after enqueuing some of its work on st (a refit copy,
@@ -777,10 +807,7 @@ int render_enqueue_body(rt_context *c, const rt_camera *cam, const rt_params *pr
 int render_enqueue(rt_context *c, const rt_camera *cam, const rt_params *prm, float *accum_rgb, hipStream_t st,
                    hipEvent_t ev_start) {
   const int r = render_enqueue_body(c, cam, prm, accum_rgb, st, ev_start);
-  if (r != RT_OK && c->ev_done && hipEventRecord(c->ev_done, st) == hipSuccess) {
-    c->last_stream = st;
-    c->have_done = true;
-  }
+  if (r != RT_OK && c->ev_done) (void)frame_end(c, st);
   return r;
 }
 
@@ -800,13 +827,35 @@ hipError_t ensure_frame(rt_context *c, size_t nf) {
 
 extern "C" {
 
+int rt_internal_frame_check(const rt_context *c, const rt_camera *cam, const rt_params *prm) {
+  if (!c || !cam || !params_ok(prm)) return RT_ERR_INVALID;
+  if (cam->model != RT_CAMERA_CPU && cam->model != RT_CAMERA_GPU) return RT_ERR_INVALID;
+  if (cam->model == RT_CAMERA_CPU && (prm->width < 2 || prm->height < 2)) return RT_ERR_INVALID;
+  if (!c->d_geom) return RT_ERR_NO_SCENE;
+  return RT_OK;
+}
+
+int rt_internal_frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, void *stream,
+                            rt_frame_setup *out) {
+  if (!out) return RT_ERR_INVALID;
+  const int r = rt_internal_frame_check(c, cam, prm);
+  if (r != RT_OK) return r;
+  return frame_begin(c, cam, prm, stream ? (hipStream_t)stream : c->stream, *out);
+}
+
+int rt_internal_frame_end(rt_context *c, hipStream_t stream) {
+  if (!c || !c->ev_done) return RT_ERR_INVALID;
+  return frame_end(c, stream);
+}
+
 int rt_render_async(rt_context *c, const rt_camera *cam, const rt_params *prm, float *accum_rgb,
                     void *stream) {
   if (!c || !cam || !params_ok(prm) || (!accum_rgb && prm->local_rows && prm->width))
     return RT_ERR_INVALID;
-  if (cam->model != RT_CAMERA_CPU && cam->model != RT_CAMERA_GPU) return RT_ERR_INVALID;
-  if (cam->model == RT_CAMERA_CPU && (prm->width < 2 || prm->height < 2)) return RT_ERR_INVALID;
-  if (!c->d_geom) return RT_ERR_NO_SCENE;
+  {
+    const int r = rt_internal_frame_check(c, cam, prm);
+    if (r != RT_OK) return r;
+  }
   return render_enqueue(c, cam, prm, accum_rgb, stream ? (hipStream_t)stream : c->stream, nullptr);
 }
 
