@@ -15,6 +15,7 @@
 //   extent; 11 = reference, 50 = 10k spheres) --scene final|five
 //   --camera cpu|gpu --semantics cpu|gpu --accel bvh|scan --gpus N --device N
 //   --devices D0,D1,... --gather rccl|host --out FILE --p6 --quiet
+//   --denoise[=ITERATIONS]
 // With --gpus N > 1 the frame is split into interleaved 8-row bands, one
 // context and stream per device; each device tonemaps its tile to bytes
 // (rt_tonemap_async) and the byte tiles are gathered to device 0 with one
@@ -24,6 +25,10 @@
 // --devices names the device of each band; a device may repeat (bands on one
 // GPU, host gather only: RCCL takes one rank per device), which runs the
 // N-band split, per-band contexts and the assembly on a single-GPU machine.
+// --denoise (one GPU only: the filter needs the whole frame) follows the render
+// with the first-hit feature pass at the same parameters (rt_aov.h) and the
+// guided a-trous filter (rt_denoise.h, its default options), in place, on the
+// same stream; write_color and the PPM path then run on the filtered sums.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -41,6 +46,8 @@
 #include <rccl/rccl.h>
 
 #include "rt.h"
+#include "rt_aov.h"
+#include "rt_denoise.h"
 
 namespace {
 
@@ -59,6 +66,8 @@ struct options {
   std::string out;
   bool p6 = false, quiet = false;
   double launch_samples = 0.0;  // RT_OPT_LAUNCH_SAMPLES (0: the library's default)
+  bool denoise = false;
+  int denoise_iterations = 0;  // --denoise=N (0: the library's default)
 };
 
 [[noreturn]] void die(const char *what, int st) {
@@ -76,7 +85,7 @@ void check(int st, const char *what) {
                "          [--spheres HALF_EXTENT] [--scene final|five] [--camera cpu|gpu]\n"
                "          [--semantics cpu|gpu] [--accel bvh|scan] [--gpus N] [--device N]\n"
                "          [--devices D0,D1,...] [--gather rccl|host] [--out FILE] [--p6] [--quiet]\n"
-               "          [--launch-samples N]\n",
+               "          [--launch-samples N] [--denoise[=ITERATIONS]]\n",
                argv0);
   std::exit(2);
 }
@@ -134,6 +143,12 @@ int main(int argc, char **argv) {
     else if (a == "--p6") o.p6 = true;
     else if (a == "--quiet") o.quiet = true;
     else if (a == "--launch-samples") o.launch_samples = std::atof(next());
+    else if (a == "--denoise") o.denoise = true;
+    else if (a.rfind("--denoise=", 0) == 0) {
+      o.denoise = true;
+      o.denoise_iterations = std::atoi(a.c_str() + 10);
+      if (o.denoise_iterations < 1 || o.denoise_iterations > 8) usage(argv[0]);
+    }
     else usage(argv[0]);
   }
   if (!height_set && (o.width != (gpu_mode ? 1920 : 1200))) {
@@ -143,6 +158,12 @@ int main(int argc, char **argv) {
   if (gpu_mode && !o.seed_set) o.seed = (unsigned long long)std::time(nullptr);  // main.cu:88
   if (o.width < 2 || o.height < 2 || o.spp < 0 || o.depth < 0 || o.gpus < 1) usage(argv[0]);
   if (o.gather != "auto" && o.gather != "rccl" && o.gather != "host") usage(argv[0]);
+  if (o.denoise && o.gpus > 1) {
+    std::fprintf(stderr, "rtow: --denoise filters a whole frame on one GPU; it cannot be combined with --gpus %d\n",
+                 o.gpus);
+    std::exit(2);
+  }
+  if (o.denoise && o.spp < 1) usage(argv[0]);
   bool repeated = false;
   if (!o.devices.empty()) {
     if ((int)o.devices.size() != o.gpus) usage(argv[0]);
@@ -258,6 +279,7 @@ int main(int argc, char **argv) {
   std::vector<float *> d_tile(o.gpus, nullptr);
   std::vector<uint8_t *> d_u8(o.gpus, nullptr);
   uint8_t *d_all = nullptr;
+  char *d_guides = nullptr;  // --denoise: hits, position, normal, albedo, then the filter's scratch
   std::vector<ncclComm_t> comms;
   if (use_rccl) {
     comms.resize(o.gpus);
@@ -281,6 +303,13 @@ int main(int argc, char **argv) {
     if (use_rccl && g == 0 && hipMalloc(&d_all, 3 * tile_px * o.gpus) != hipSuccess)
       die("gather buffer", RT_ERR_HIP);
   }
+  const size_t guide_bytes = (4 + 3 * 12) * tile_px;
+  if (o.denoise) {
+    // the four guide buffers, then (16-byte aligned) the filter's scratch
+    const size_t scratch = rt_denoise_scratch_bytes(o.width, o.height);
+    if (scratch == 0) die("--denoise: frame size", RT_ERR_INVALID);
+    if (hipMalloc(&d_guides, (guide_bytes + 15) / 16 * 16 + scratch) != hipSuccess) die("denoise buffers", RT_ERR_HIP);
+  }
   // per device: events before the render, after it, after write_color and
   // after the gather, for the per-device lines on stderr
   std::vector<hipEvent_t> ev(4 * (size_t)o.gpus, nullptr);
@@ -296,6 +325,26 @@ int main(int argc, char **argv) {
     (void)hipEventRecord(ev[4 * g + 0], streams[g]);
     check(rt_render_async(ctxs[g], &cam, &jobs[g].params, d_tile[g], streams[g]), "rt_render_async");
     (void)hipEventRecord(ev[4 * g + 1], streams[g]);
+    if (o.denoise) {
+      rt_aov_buffers gb{};
+      gb.hits = reinterpret_cast<uint32_t *>(d_guides);
+      gb.position = reinterpret_cast<float *>(d_guides + 4 * tile_px);
+      gb.normal = gb.position + 3 * tile_px;
+      gb.albedo = gb.normal + 3 * tile_px;
+      check(rt_aov_async(ctxs[g], &cam, &jobs[g].params, &gb, streams[g]), "rt_aov_async");
+      rt_denoise_desc dd{};
+      dd.width = o.width;
+      dd.height = o.height;
+      dd.spp = o.spp;
+      dd.iterations = o.denoise_iterations;
+      dd.beauty = d_tile[g];
+      dd.hits = gb.hits;
+      dd.position = gb.position;
+      dd.normal = gb.normal;
+      dd.albedo = gb.albedo;
+      dd.out = d_tile[g];
+      check(rt_denoise_async(ctxs[g], &dd, d_guides + (guide_bytes + 15) / 16 * 16, streams[g]), "rt_denoise_async");
+    }
     check(rt_tonemap_async(ctxs[g], d_tile[g], tile_px, o.spp > 0 ? o.spp : 1, tone_mode, d_u8[g], streams[g]),
           "rt_tonemap_async");
     (void)hipEventRecord(ev[4 * g + 2], streams[g]);
@@ -385,8 +434,9 @@ int main(int argc, char **argv) {
       (void)hipEventElapsedTime(&r, ev[4 * g + 0], ev[4 * g + 1]);
       (void)hipEventElapsedTime(&t, ev[4 * g + 1], ev[4 * g + 2]);
       (void)hipEventElapsedTime(&x, ev[4 * g + 2], ev[4 * g + 3]);
-      std::fprintf(stderr, "GPU %d (device %d): render %.3f ms in %llu launch(es), write_color %.3f ms, %s %.3f ms\n",
-                   g, devs[g], r, (unsigned long long)jobs[g].stats.launches, t,
+      std::fprintf(stderr, "GPU %d (device %d): render %.3f ms in %llu launch(es), %s %.3f ms, %s %.3f ms\n",
+                   g, devs[g], r, (unsigned long long)jobs[g].stats.launches,
+                   o.denoise ? "feature pass + denoise + write_color" : "write_color", t,
                    use_rccl ? "gather (RCCL)" : "gather (none)", x);
     }
   }
@@ -423,6 +473,7 @@ int main(int argc, char **argv) {
     (void)hipSetDevice(devs[0]);
     (void)hipFree(d_all);
   }
+  (void)hipFree(d_guides);
   for (auto *c : ctxs) rt_context_destroy(c);
   if (!o.quiet && !gpu_mode) std::fprintf(stderr, "\nDone.\n");  // main.cc:132
   return 0;

@@ -563,7 +563,9 @@ launch_plan plan_launches(const rt_params *prm, double launch_samples) {
 // (rt_internal_frame_begin: the render below and librtow_aov.so's first-hit
 // pass): the device, the wait on the context's previous pass, the kernel
 // arguments and the layer grid's refit for this frame geometry.
-int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipStream_t st, rt_frame_setup &fs) {
+// (pass_begin alone, rt_internal_pass_begin: a pass that reads no scene,
+// librtow_denoise.so's filter)
+int pass_begin(rt_context *c, hipStream_t st, rt_frame_setup &fs) {
   std::memset(&fs, 0, sizeof fs);
   fs.stream = st;
   fs.placement = rtk::kGridGlobal;
@@ -574,6 +576,14 @@ int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipSt
   // passes of one context are serialised, whatever streams they come on:
   // they share the block-order scratch buffer and the grid's buffers
   if (c->have_done && c->last_stream != st) RT_HIP(hipStreamWaitEvent(st, c->ev_done, 0));
+  return RT_OK;
+}
+
+int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipStream_t st, rt_frame_setup &fs) {
+  {
+    const int r = pass_begin(c, st, fs);
+    if (r != RT_OK) return r;
+  }
   if (prm->width == 0 || prm->local_rows == 0) return RT_OK;  // nothing to launch
   rtk::kparams &kp = fs.kp;
   fill_kparams(c, cam, prm, nullptr, kp);
@@ -841,6 +851,11 @@ int rt_internal_frame_begin(rt_context *c, const rt_camera *cam, const rt_params
   const int r = rt_internal_frame_check(c, cam, prm);
   if (r != RT_OK) return r;
   return frame_begin(c, cam, prm, stream ? (hipStream_t)stream : c->stream, *out);
+}
+
+int rt_internal_pass_begin(rt_context *c, void *stream, rt_frame_setup *out) {
+  if (!c || !out) return RT_ERR_INVALID;
+  return pass_begin(c, stream ? (hipStream_t)stream : c->stream, *out);
 }
 
 int rt_internal_frame_end(rt_context *c, hipStream_t stream) {

@@ -1,6 +1,7 @@
 // rt_frame.h -- internal: how a pass over the context's scene (the render in
-// rt_api.cpp, the first-hit feature pass in rt_aov.hip / librtow_aov.so)
-// starts and ends on a stream.  Not installed; rt_context stays opaque outside
+// rt_api.cpp, the first-hit feature pass in rt_aov.hip / librtow_aov.so), or a
+// pass that only shares the context's ordering (the denoiser in
+// rt_denoise.hip / librtow_denoise.so), starts and ends on a stream.  Not installed; rt_context stays opaque outside
 // rt_api.cpp, so the second library gets what it needs through this struct.
 #ifndef RTOW_RT_FRAME_H
 #define RTOW_RT_FRAME_H
@@ -32,6 +33,12 @@ int rt_internal_frame_check(const rt_context *ctx, const rt_camera *cam, const r
 // Arguments as checked by rt_internal_frame_check.
 int rt_internal_frame_begin(rt_context *ctx, const rt_camera *cam, const rt_params *params, void *stream,
                             rt_frame_setup *out);
+
+// The same for a pass that reads no scene (librtow_denoise.so): hipSetDevice
+// and the wait on the context's previous pass; of *out only stream, ev0 and
+// ev1 are set, the rest is zero.  RT_ERR_INVALID for a NULL argument, no HIP
+// call before that.  Ends with rt_internal_frame_end like the others.
+int rt_internal_pass_begin(rt_context *ctx, void *stream, rt_frame_setup *out);
 
 // After the pass's last launch (also when enqueuing failed half way): records
 // the context's ev_done on the stream, so that renders, feature passes and

@@ -24,6 +24,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RTOW_LIB") or os.path.join(HERE, "librtow.so")
 # the first-hit feature pass (include/rt_aov.h): a second library next to librtow.so
 AOV_LIB_PATH = os.path.join(HERE, "librtow_aov.so")
+# the guided a-trous denoiser (include/rt_denoise.h): a third library on the same terms
+DENOISE_LIB_PATH = os.path.join(HERE, "librtow_denoise.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
@@ -44,6 +46,10 @@ AOV_VERSION = 1  # include/rt_aov.h RT_AOV_VERSION
 # rt_aov_buffers' fields in order: (name, numpy dtype, channels)
 AOV_FIELDS = (("hits", np.uint32, 1), ("id", np.int32, 1), ("depth", np.float32, 1),
               ("position", np.float32, 3), ("normal", np.float32, 3), ("albedo", np.float32, 3))
+DENOISE_VERSION = 1  # include/rt_denoise.h RT_DENOISE_VERSION
+# rt_denoise_desc's input pointers in order, and its options with their defaults
+DENOISE_INPUTS = ("beauty", "hits", "position", "normal", "albedo")
+DENOISE_DEFAULTS = {"iterations": 5, "normal_power": 6, "sigma_plane": 0.5, "sigma_color": 0.15}
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
 RT_OPT_BVH_COLLAPSE, RT_OPT_BVH_SIDE, RT_OPT_LAUNCH_SAMPLES, RT_OPT_GRID_FIT = 4, 5, 6, 7
@@ -99,8 +105,59 @@ class AovBuffers(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name, _, _ in AOV_FIELDS]
 
 
+class DenoiseDesc(ctypes.Structure):
+    """rt_denoise_desc: the frame, the options (0 = default) and device
+    (rt_denoise_async) or host (rt_denoise) pointers."""
+    _fields_ = ([(name, ctypes.c_int32) for name in ("width", "height", "spp", "iterations", "normal_power")] +
+                [("sigma_plane", ctypes.c_float), ("sigma_color", ctypes.c_float), ("reserved", ctypes.c_int32)] +
+                [(name, ctypes.c_void_p) for name in DENOISE_INPUTS + ("out",)])
+
+
 _lib = None
 _aov_lib = None
+_denoise_lib = None
+
+
+def denoise_lib():
+    """Load librtow_denoise.so, the guided a-trous filter (raises if it has
+    not been built).  librtow.so loads first: the filter runs on its contexts."""
+    global _denoise_lib
+    if _denoise_lib is None:
+        lib()
+        if not os.path.exists(DENOISE_LIB_PATH):
+            raise RuntimeError(f"{DENOISE_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or make -C ray-tracing-in-one-weekend_amd)")
+        L = ctypes.CDLL(DENOISE_LIB_PATH)
+        L.rt_denoise_version.restype = ctypes.c_int
+        L.rt_denoise_scratch_bytes.restype = ctypes.c_size_t
+        L.rt_denoise_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.rt_denoise_async.argtypes = [ctypes.c_void_p, ctypes.POINTER(DenoiseDesc), ctypes.c_void_p,
+                                       ctypes.c_void_p]
+        L.rt_denoise.argtypes = [ctypes.c_void_p, ctypes.POINTER(DenoiseDesc), ctypes.POINTER(ctypes.c_double)]
+        if L.rt_denoise_version() != DENOISE_VERSION:
+            raise RuntimeError(f"{DENOISE_LIB_PATH}: RT_DENOISE_VERSION {L.rt_denoise_version()}, "
+                               f"expected {DENOISE_VERSION}")
+        _denoise_lib = L
+    return _denoise_lib
+
+
+def denoise_desc(width, height, spp, **options):
+    """A DenoiseDesc without pointers.  Options (DENOISE_DEFAULTS) left out or
+    None take their defaults; here a value means itself, so normal_power=0 is
+    "no squaring" and sigma_color=0 / sigma_plane=inf switch their terms off
+    (the struct's own 0 = default and -1 = off encoding stays inside)."""
+    unknown = [k for k in options if k not in DENOISE_DEFAULTS]
+    if unknown:
+        raise ValueError(f"unknown denoise options {unknown}")
+    opt = {k: v for k, v in options.items() if v is not None}
+    if opt.get("iterations", 1) == 0 or opt.get("sigma_plane", 1) == 0:
+        raise ValueError("iterations and sigma_plane must be positive")
+    d = DenoiseDesc(width=width, height=height, spp=spp)
+    d.iterations = int(opt.get("iterations", 0))
+    d.normal_power = int(opt["normal_power"]) or -1 if "normal_power" in opt else 0
+    d.sigma_plane = float(opt.get("sigma_plane", 0.0))
+    d.sigma_color = (float(opt["sigma_color"]) or -1.0) if "sigma_color" in opt else 0.0
+    return d
 
 
 def aov_lib():
@@ -436,6 +493,46 @@ class Context:
             setattr(bufs, name, ptr)
         check(aov_lib().rt_aov_async(self._h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(bufs),
                                      ctypes.c_void_p(stream)), "rt_aov_async")
+
+    def denoise(self, beauty, aov, spp, **options):
+        """The guided a-trous filter (rt_denoise, include/rt_denoise.h),
+        synchronously, on host arrays: beauty (H, W, 3) float32 sums of a
+        whole frame, aov the dict Context.aov returns for the same parameters
+        ("hits", "position", "normal", "albedo" are read).  Options:
+        DENOISE_DEFAULTS (see denoise_desc).  Returns the filtered sums
+        (H, W, 3) float32; self.denoise_ms holds the launches' event time."""
+        d = denoise_desc(int(np.shape(beauty)[1]), int(np.shape(beauty)[0]), spp, **options)
+        missing = [k for k in DENOISE_INPUTS[1:] if k not in aov]
+        if missing:
+            raise ValueError(f"feature buffers {missing} are missing")
+        keep = {"beauty": np.ascontiguousarray(beauty, np.float32),
+                "hits": np.ascontiguousarray(aov["hits"], np.uint32)}
+        for k in DENOISE_INPUTS[2:]:
+            keep[k] = np.ascontiguousarray(aov[k], np.float32)
+        for k, a in keep.items():
+            if a.shape != (d.height, d.width) + ((3,) if k != "hits" else ()):
+                raise ValueError(f"{k}: shape {a.shape} does not match the {d.width} x {d.height} frame")
+            setattr(d, k, a.ctypes.data)
+        out = np.zeros((d.height, d.width, 3), np.float32)
+        d.out = out.ctypes.data
+        ms = ctypes.c_double()
+        check(denoise_lib().rt_denoise(self._h, ctypes.byref(d), ctypes.byref(ms)), "rt_denoise")
+        self.denoise_ms = ms.value
+        return out
+
+    def denoise_async(self, dev_ptrs, width, height, spp, scratch_ptr, stream=0, **options):
+        """Enqueue the filter (rt_denoise_async) on raw device pointers (e.g.
+        torch tensor.data_ptr()): dev_ptrs maps DENOISE_INPUTS and "out" to
+        device pointers ("out" may be the beauty buffer), scratch_ptr is
+        denoise_lib().rt_denoise_scratch_bytes(width, height) bytes."""
+        unknown = [k for k in dev_ptrs if k not in DENOISE_INPUTS + ("out",)]
+        if unknown:
+            raise ValueError(f"unknown denoise buffers {unknown}")
+        d = denoise_desc(width, height, spp, **options)
+        for name, ptr in dev_ptrs.items():
+            setattr(d, name, ptr)
+        check(denoise_lib().rt_denoise_async(self._h, ctypes.byref(d), ctypes.c_void_p(scratch_ptr),
+                                             ctypes.c_void_p(stream)), "rt_denoise_async")
 
     def tonemap_async(self, dev_sums, n_pixels, spp, dev_out, mode=RT_TONEMAP_CPU, stream=0):
         """write_color on the device: fp32 sums -> bytes, both device pointers."""
