@@ -42,7 +42,6 @@ struct bvh_builder {
   int max_leaf = kLeaf;
   double collapse_area = 0.35;
   double side_weight = 1.0;  // SAH weight of the x- and z-facing sides
-  double grid_scale = 1.0;   // layer-grid cell side multiplier
   double grid_phase_x = 0.0, grid_phase_z = 0.0;  // grid origin shifted by these fractions of a cell, [0, 1)
 
   double area(const box &b) const {
@@ -271,16 +270,23 @@ struct bvh_builder {
   }
   // Layer grid: square x-z cells of side g over the layer spheres' padded
   // boxes; a cell lists every layer sphere whose padded box comes within pad
-  // of it.  g is chosen for ~1 sphere per cell (grid_scale scales it);
-  // cells list at most 15 spheres (else g shrinks).
-  std::vector<uint32_t> grid_cells;
-  std::vector<float> grid_items;  // 4 floats per item
-  float grid_x0 = 0, grid_z0 = 0, grid_xi = 0, grid_zi = 0, grid_x1 = 0, grid_z1 = 0, grid_g = 0;
-  int grid_nx = 0, grid_nz = 0;
+  // of it.  g is chosen for ~1 sphere per cell (grid.scale scales it: the
+  // builder's input, RT_OPT_GRID_SCALE or a fitter's candidate; build_grid
+  // rebuilds the rest of grid from it); cells list at most 15 spheres (else g
+  // shrinks).  cells empty: no grid.
+  grid_geom grid;
+  void configure(const accel_options &o, double scale) {
+    max_leaf = std::max(1, std::min(kLeaf, o.bvh_leaf));
+    collapse_area = o.collapse;
+    side_weight = o.side;
+    grid.scale = scale;
+    grid_phase_x = o.grid_phase_x;
+    grid_phase_z = o.grid_phase_z;
+  }
   void build_grid(const rt_scene_view *s, uint32_t n_tree) {
-    grid_cells.clear();
-    grid_items.clear();
-    grid_nx = grid_nz = 0;
+    grid.cells.clear();  // (the vectors keep their capacity from build to build)
+    grid.items.clear();
+    grid.nx = grid.nz = 0;
     double x0 = 1e300, x1 = -1e300, z0 = 1e300, z1 = -1e300;
     for (uint32_t k = 0; k < n_tree; ++k) {
       const uint32_t i = ord[k];
@@ -294,7 +300,7 @@ struct bvh_builder {
     z0 -= 2 * pad;
     x1 += 2 * pad;
     z1 += 2 * pad;
-    double g = grid_scale * std::sqrt((x1 - x0) * (z1 - z0) / (double)n_tree);
+    double g = grid.scale * std::sqrt((x1 - x0) * (z1 - z0) / (double)n_tree);
     const double bx0 = x0, bz0 = z0;
     for (int attempt = 0; attempt < 8; ++attempt, g *= 0.8) {
       // the phase moves the cell borders relative to the spheres (the image is
@@ -324,40 +330,40 @@ struct bvh_builder {
       const int rx = nx + 2, rz = nz + 2;
       // in stored (ring) order, every cell's first item is the running item
       // count, ring cells included: cell rc's items are [first_rc, first_rc+1)
-      grid_cells.assign((size_t)rx * rz, 0);
-      grid_items.clear();
-      for (size_t rc = 0; rc < grid_cells.size(); ++rc) {
+      grid.cells.assign((size_t)rx * rz, 0);
+      grid.items.clear();
+      for (size_t rc = 0; rc < grid.cells.size(); ++rc) {
         const int a = (int)(rc % rx) - 1, b = (int)(rc / rx) - 1;
         const bool listed = a >= 0 && a < nx && b >= 0 && b < nz;
         const size_t c = listed ? (size_t)b * nx + a : 0;
-        grid_cells[rc] = (uint32_t)(grid_items.size() / 4) << 4 | (listed ? (uint32_t)lists[c].size() : 0u);
+        grid.cells[rc] = (uint32_t)(grid.items.size() / 4) << 4 | (listed ? (uint32_t)lists[c].size() : 0u);
         if (!listed) continue;
         for (uint32_t i : lists[c]) {
           const double x = s->cx[i], y = s->cy[i], z = s->cz[i], r = s->radius[i];
-          grid_items.push_back(s->cx[i]);
-          grid_items.push_back(s->cz[i]);
-          grid_items.push_back((float)(x * x + y * y + z * z - r * r));
+          grid.items.push_back(s->cx[i]);
+          grid.items.push_back(s->cz[i]);
+          grid.items.push_back((float)(x * x + y * y + z * z - r * r));
           // the tie key of the closed interval: 2 (0x7fffffff - index)
           const uint32_t tie2 = (0x7fffffffu - i) << 1;
           float f;
           std::memcpy(&f, &tie2, 4);
-          grid_items.push_back(f);
+          grid.items.push_back(f);
         }
       }
-      if (grid_items.size() / 4 >= (1u << 27)) {
-        grid_cells.clear();
-        grid_items.clear();
+      if (grid.items.size() / 4 >= (1u << 27)) {
+        grid.cells.clear();
+        grid.items.clear();
         return;
       }
-      grid_x0 = (float)(x0 - g);
-      grid_z0 = (float)(z0 - g);
-      grid_xi = (float)x0;
-      grid_zi = (float)z0;
-      grid_g = (float)g;
-      grid_nx = rx;
-      grid_nz = rz;
-      grid_x1 = (float)(x0 + nx * g);
-      grid_z1 = (float)(z0 + nz * g);
+      grid.x0 = (float)(x0 - g);
+      grid.z0 = (float)(z0 - g);
+      grid.xi = (float)x0;
+      grid.zi = (float)z0;
+      grid.g = (float)g;
+      grid.nx = rx;
+      grid.nz = rz;
+      grid.x1 = (float)(x0 + nx * g);
+      grid.z1 = (float)(z0 + nz * g);
       return;
     }
   }
@@ -533,12 +539,7 @@ void build_accel(const rt_scene_view *s, const accel_options &o, accel_build &a,
     r.sealed = sealed[i];
   }
   bvh_builder bb;
-  bb.max_leaf = std::max(1, std::min(bvh_builder::kLeaf, o.bvh_leaf));
-  bb.collapse_area = o.collapse;
-  bb.side_weight = o.side;
-  bb.grid_scale = o.grid_scale;
-  bb.grid_phase_x = o.grid_phase_x;
-  bb.grid_phase_z = o.grid_phase_z;
+  bb.configure(o, o.grid_scale);
   bb.run(s);
   // Grid placement.  The whole grid in LDS when it fits the
   // per-block budget (u16 LDS addresses: < 4096 items); else, for auto or
@@ -547,27 +548,27 @@ void build_accel(const rt_scene_view *s, const accel_options &o, accel_build &a,
   // else global memory.
   int place = kGridGlobal;
   const size_t lds_max = o.wide ? kGridLdsMaxWide : kGridLdsMax;
-  const auto n_items = [&] { return (long long)(bb.grid_items.size() / 4); };
-  const auto n_cells = [&] { return (long long)bb.grid_cells.size(); };
-  if (!bb.grid_cells.empty()) {
+  const auto n_items = [&] { return (long long)(bb.grid.items.size() / 4); };
+  const auto n_cells = [&] { return (long long)bb.grid.cells.size(); };
+  if (!bb.grid.cells.empty()) {
     const bool lds_fits = n_items() < 4096 && grid_lds_bytes(kGridLds, n_items(), n_cells()) <= lds_max;
     if ((o.grid_placement < 0 || o.grid_placement == kGridLds) && lds_fits) {
       place = kGridLds;
     } else if (o.grid_placement < 0 || o.grid_placement == kGridCells) {
-      const double scale0 = bb.grid_scale;
-      for (int k = 0; k < 8 && !bb.grid_cells.empty(); ++k) {
+      const double scale0 = bb.grid.scale;
+      for (int k = 0; k < 8 && !bb.grid.cells.empty(); ++k) {
         const size_t need = grid_lds_bytes(kGridCells, n_items(), n_cells());
         if (need <= lds_max && n_items() < 65536) {
           place = kGridCells;
           break;
         }
         const double grow = std::max(1.02, 1.01 * std::sqrt((double)need / (double)lds_max));
-        if (bb.grid_scale * grow > 1.6 * scale0) break;
-        bb.grid_scale *= grow;
+        if (bb.grid.scale * grow > 1.6 * scale0) break;
+        bb.grid.scale *= grow;
         bb.build_grid(s, bb.n_layer);
       }
-      if (place != kGridCells && bb.grid_scale != scale0) {  // back to the requested cells
-        bb.grid_scale = scale0;
+      if (place != kGridCells && bb.grid.scale != scale0) {  // back to the requested cells
+        bb.grid.scale = scale0;
         bb.build_grid(s, bb.n_layer);
       }
     }
@@ -584,22 +585,11 @@ void build_accel(const rt_scene_view *s, const accel_options &o, accel_build &a,
   a.layer_cy = bb.layer_cy;
   a.extra_pair0 = bb.extra_pair0;
   a.n_extra_pairs = bb.n_extra_pairs;
-  a.grid_cells = bb.grid_cells;
-  a.grid_items = bb.grid_items;
-  a.grid_x0 = bb.grid_x0;
-  a.grid_z0 = bb.grid_z0;
-  a.grid_xi = bb.grid_xi;
-  a.grid_zi = bb.grid_zi;
-  a.grid_x1 = bb.grid_x1;
-  a.grid_z1 = bb.grid_z1;
-  a.grid_g = bb.grid_g;
-  a.grid_nx = bb.grid_nx;
-  a.grid_nz = bb.grid_nz;
-  a.grid_scale = bb.grid_scale;
-  a.grid_placement = bb.grid_cells.empty() ? kGridGlobal : place;
+  a.grid = bb.grid;
+  a.grid_placement = bb.grid.cells.empty() ? kGridGlobal : place;
   // the builder's layer split and boxes go on into the grid fitter
-  if (fitter && !bb.grid_cells.empty())
-    *fitter = grid_fitter::make_from(s, o, a.grid_placement, bb.grid_scale, &bb);
+  if (fitter && !bb.grid.cells.empty())
+    *fitter = grid_fitter::make_from(s, o, a.grid_placement, bb.grid.scale, &bb);
 }
 
 // ---------------------------------------------------------- grid fitter --
@@ -614,10 +604,10 @@ struct grid_fitter::impl {
   double s0 = 1.0;
   // the grid at scale s into bb's grid fields; false if it does not fit the placement
   bool grid_at(double scale) const {
-    bb.grid_scale = scale;
+    bb.grid.scale = scale;
     bb.build_grid(&view, bb.n_layer);
-    if (bb.grid_cells.empty()) return false;
-    const long long items = (long long)(bb.grid_items.size() / 4), cells = (long long)bb.grid_cells.size();
+    if (bb.grid.cells.empty()) return false;
+    const long long items = (long long)(bb.grid.items.size() / 4), cells = (long long)bb.grid.cells.size();
     if (placement == kGridLds)
       return items < 4096 && grid_lds_bytes(kGridLds, items, cells) <= lds_max;
     return items < 65536 && grid_lds_bytes(kGridCells, items, cells) <= lds_max;
@@ -653,12 +643,7 @@ grid_fitter *grid_fitter::make_from(const rt_scene_view *s, const accel_options 
   if (builder) {
     q->bb = std::move(*static_cast<bvh_builder *>(builder));
   } else {
-    q->bb.max_leaf = std::max(1, std::min(bvh_builder::kLeaf, o.bvh_leaf));
-    q->bb.collapse_area = o.collapse;
-    q->bb.side_weight = o.side;
-    q->bb.grid_scale = scale0;
-    q->bb.grid_phase_x = o.grid_phase_x;
-    q->bb.grid_phase_z = o.grid_phase_z;
+    q->bb.configure(o, scale0);
     q->bb.run(&q->view);
   }
   q->placement = placement;
@@ -683,8 +668,8 @@ double grid_fitter::choose(const rt_camera &cam, int width, int height,
     const double scale = q.s0 * (1.0 + 0.01 * k);
     if (!q.grid_at(scale)) continue;
     const bvh_builder &b = q.bb;
-    const int nx = b.grid_nx, nz = b.grid_nz;
-    const double g = b.grid_g;
+    const int nx = b.grid.nx, nz = b.grid.nz;
+    const double g = b.grid.g;
     // where 64 x 64 camera directions over the frame meet the layer plane
     std::vector<double> w((size_t)nx * nz, 0.0);
     constexpr int kS = 64;
@@ -700,7 +685,7 @@ double grid_fitter::choose(const rt_camera &cam, int width, int height,
         if (!(d[1] != 0.0)) continue;
         const double t = (b.layer_cy - cam.eye[1]) / d[1];
         if (!(t > 0.0)) continue;
-        const double x = (cam.eye[0] + t * d[0] - b.grid_x0) / g, z = (cam.eye[2] + t * d[2] - b.grid_z0) / g;
+        const double x = (cam.eye[0] + t * d[0] - b.grid.x0) / g, z = (cam.eye[2] + t * d[2] - b.grid.z0) / g;
         if (!(x >= 0.0 && x < nx && z >= 0.0 && z < nz)) continue;
         w[(size_t)z * nx + (size_t)x] += 1.0;
       }
@@ -715,7 +700,7 @@ double grid_fitter::choose(const rt_camera &cam, int width, int height,
             if (zz >= 0 && zz < nz && xx >= 0 && xx < nx) v += w[(size_t)zz * nx + xx];
           }
         sw += v;
-        swi += v * (double)(b.grid_cells[(size_t)z * nx + x] & 15u);
+        swi += v * (double)(b.grid.cells[(size_t)z * nx + x] & 15u);
       }
     if (!(sw > 0.0)) return q.s0;  // the camera does not see the layer: the builder's grid
     const double cost = (swi / sw + kFitCellCost) / g;
@@ -731,19 +716,7 @@ double grid_fitter::choose(const rt_camera &cam, int width, int height,
 bool grid_fitter::build(double scale, grid_geom &out) const {
   const impl &q = *p_;
   if (!q.grid_at(scale)) return false;
-  const bvh_builder &b = q.bb;
-  out.cells = b.grid_cells;
-  out.items = b.grid_items;
-  out.x0 = b.grid_x0;
-  out.z0 = b.grid_z0;
-  out.xi = b.grid_xi;
-  out.zi = b.grid_zi;
-  out.x1 = b.grid_x1;
-  out.z1 = b.grid_z1;
-  out.g = b.grid_g;
-  out.nx = b.grid_nx;
-  out.nz = b.grid_nz;
-  out.scale = b.grid_scale;
+  out = q.bb.grid;
   return true;
 }
 

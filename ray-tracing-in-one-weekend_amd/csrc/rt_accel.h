@@ -5,6 +5,7 @@
 #define RTOW_RT_ACCEL_H
 
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "rt_internal.h"
@@ -24,6 +25,28 @@ struct accel_options {
   bool wide = false;         // 64-bit pixel sums (an albedo above 1): less LDS for the grid
 };
 
+// The layer grid's geometry, in one spelling from the builder to the context
+// (grid_kparams in rt_api.cpp turns it into the kernel's): the stored cells'
+// origin (x0, z0), the listed region [xi, x1) x [zi, z1), the cell side g, the
+// stored counts nx x nz (ring included) and the cell scale it was built with.
+struct grid_dims {
+  float x0 = 0, z0 = 0, xi = 0, zi = 0, x1 = 0, z1 = 0, g = 0;
+  int nx = 0, nz = 0;
+  double scale = 1.0;
+  bool operator==(const grid_dims &o) const {
+    return x0 == o.x0 && z0 == o.z0 && xi == o.xi && zi == o.zi && x1 == o.x1 && z1 == o.z1 && g == o.g &&
+           nx == o.nx && nz == o.nz && scale == o.scale;
+  }
+};
+struct grid_geom : grid_dims {
+  std::vector<uint32_t> cells;
+  std::vector<float> items;  // 4 floats per item (the fourth a tie key's bits: compared as bits)
+  bool operator==(const grid_geom &o) const {
+    return grid_dims::operator==(o) && cells == o.cells && items.size() == o.items.size() &&
+           (items.empty() || !std::memcmp(items.data(), o.items.data(), items.size() * sizeof(float)));
+  }
+};
+
 // everything rt_scene_upload copies to the device, plus the builder's facts
 struct accel_build {
   uint32_t n = 0, n_pad = 0;
@@ -37,12 +60,7 @@ struct accel_build {
   bool layer_mode = false;
   float layer_lo = 0.0f, layer_hi = 0.0f, layer_cy = 0.0f;
   uint32_t extra_pair0 = 0, n_extra_pairs = 0;
-  // layer grid (empty: none)
-  std::vector<uint32_t> grid_cells;
-  std::vector<float> grid_items;  // 4 floats per item
-  float grid_x0 = 0, grid_z0 = 0, grid_xi = 0, grid_zi = 0, grid_x1 = 0, grid_z1 = 0, grid_g = 0;
-  int grid_nx = 0, grid_nz = 0;
-  double grid_scale = 1.0;        // the cell scale the grid was built with
+  grid_geom grid;                        // layer grid (cells empty: none)
   int grid_placement = kGridGlobal;
 };
 
@@ -59,13 +77,6 @@ struct accel_build {
 // scale on C4's share and the best on the headline frame (tools/grid_fit.py).
 constexpr int kFitSteps = 30;
 constexpr double kFitCellCost = 0.5;
-struct grid_geom {
-  std::vector<uint32_t> cells;
-  std::vector<float> items;  // 4 floats per item
-  float x0 = 0, z0 = 0, xi = 0, zi = 0, x1 = 0, z1 = 0, g = 0;
-  int nx = 0, nz = 0;
-  double scale = 1.0;
-};
 class grid_fitter {
  public:
   // nullptr unless the scene walks a layer grid in an LDS placement

@@ -31,8 +31,6 @@
 #include "rt_device.h"
 #include "rt_frame.h"
 
-extern "C" void rt_internal_set_hip_error(int e);
-
 namespace rtk {
 
 // closest_hit<> re-reads its parameters with kernargs(), a kparams at offset 0
@@ -205,17 +203,6 @@ hipError_t ensure_turn_table() {
 
 namespace {
 
-int hip_fail(hipError_t e) {
-  rt_internal_set_hip_error((int)e);
-  return RT_ERR_HIP;
-}
-
-#define RT_HIP(call)                           \
-  do {                                         \
-    hipError_t _e = (call);                    \
-    if (_e != hipSuccess) return hip_fail(_e); \
-  } while (0)
-
 bool any_wanted(const rt_aov_buffers *b) {
   return b->hits || b->id || b->depth || b->position || b->normal || b->albedo;
 }
@@ -234,9 +221,7 @@ int aov_launches(const rt_frame_setup &fs, const rt_params *prm, const rt_aov_bu
   ap.position = dev->position;
   ap.normal = dev->normal;
   ap.albedo = dev->albedo;
-  const long long tiles_y = (prm->local_rows + rtk::kTile - 1) / rtk::kTile;
-  const long long tiles = (long long)fs.kp.tiles_x * tiles_y;
-  const unsigned blocks = (unsigned)((tiles + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock);
+  const unsigned blocks = (unsigned)rt_frame_blocks(prm);
   const bool bvh = (prm->flags & RT_FLAG_ACCEL_BVH) != 0;
   const int walk = !bvh ? 0 : (fs.grid ? 2 + fs.placement : 1);
   const int v = ((prm->flags & RT_FLAG_OPEN_INTERVAL) ? 1 : 0) | (walk << 1);
@@ -261,63 +246,56 @@ int aov_launches(const rt_frame_setup &fs, const rt_params *prm, const rt_aov_bu
   return RT_OK;
 }
 
-// One pass.  host == nullptr: rt_aov_async (bufs are device pointers, nothing
+// One pass.  host false: rt_aov_async (bufs are device pointers, nothing
 // waits).  Else rt_aov: bufs are host pointers; the pass runs into one device
 // allocation on the context's stream, timed by the context's events, and is
 // waited for launch by launch.  Whatever was enqueued, the pass ends with the
-// context's ev_done recorded on its stream.
+// context's ev_done recorded on its stream (rt_pass_scope).
 int aov_pass(rt_context *c, const rt_camera *cam, const rt_params *prm, const rt_aov_buffers *bufs, void *stream,
              bool host, double *kernel_ms) {
   const size_t npx = (size_t)prm->width * (size_t)prm->local_rows;
   void *const hp[6] = {bufs->hits, bufs->id, bufs->depth, bufs->position, bufs->normal, bufs->albedo};
   const size_t bytes[6] = {4 * npx, 4 * npx, 4 * npx, 12 * npx, 12 * npx, 12 * npx};
-  size_t off[6], total = 0;  // the wanted buffers' 256-byte aligned parts of the allocation
-  for (int k = 0; k < 6; ++k) {
-    off[k] = total;
-    if (hp[k]) total += (bytes[k] + 255) / 256 * 256;
-  }
-  rt_frame_setup fs;
-  std::memset(&fs, 0, sizeof fs);
+  rt_staging stage;  // rt_aov: the wanted buffers' parts of the allocation
+  size_t off[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < 6; ++k)
+    if (hp[k]) off[k] = stage.add(bytes[k]);
   std::vector<hipEvent_t> events;
-  char *d = nullptr;
-  hipError_t e = hipSuccess;
-  int r = rt_internal_frame_begin(c, cam, prm, host ? nullptr : stream, &fs);  // (sets the device)
-  const bool run = r == RT_OK && npx > 0;
-  if (run) {
-    rt_aov_buffers dev = *bufs;
-    if (host) {
-      e = hipMalloc((void **)&d, total);
-      dev.hits = hp[0] ? (uint32_t *)(d + off[0]) : nullptr;
-      dev.id = hp[1] ? (int32_t *)(d + off[1]) : nullptr;
-      dev.depth = hp[2] ? (float *)(d + off[2]) : nullptr;
-      dev.position = hp[3] ? (float *)(d + off[3]) : nullptr;
-      dev.normal = hp[4] ? (float *)(d + off[4]) : nullptr;
-      dev.albedo = hp[5] ? (float *)(d + off[5]) : nullptr;
-      if (e == hipSuccess) e = hipEventRecord(fs.ev0, fs.stream);
-    }
-    if (e == hipSuccess) r = aov_launches(fs, prm, &dev, host ? &events : nullptr);
-    if (e == hipSuccess && r == RT_OK && host) e = hipEventRecord(fs.ev1, fs.stream);
-  }
-  if (fs.stream) {
-    const int re = rt_internal_frame_end(c, fs.stream);
-    if (r == RT_OK && e == hipSuccess) r = re;
-  }
-  if (host && run) {
-    const bool ok = r == RT_OK && e == hipSuccess;
+  rt_pass_scope ps(c, cam, prm, host ? nullptr : stream);  // (sets the device)
+  const rt_frame_setup &fs = ps.fs;
+  if (ps.status != RT_OK || npx == 0) return ps.end(ps.status);
+  if (!host) return ps.end(aov_launches(fs, prm, bufs, nullptr));
+  const auto enqueue = [&]() -> int {
+    RT_HIP(stage.alloc());
+    rt_aov_buffers dev;
+    dev.hits = hp[0] ? stage.at<uint32_t>(off[0]) : nullptr;
+    dev.id = hp[1] ? stage.at<int32_t>(off[1]) : nullptr;
+    dev.depth = hp[2] ? stage.at<float>(off[2]) : nullptr;
+    dev.position = hp[3] ? stage.at<float>(off[3]) : nullptr;
+    dev.normal = hp[4] ? stage.at<float>(off[4]) : nullptr;
+    dev.albedo = hp[5] ? stage.at<float>(off[5]) : nullptr;
+    RT_HIP(hipEventRecord(fs.ev0, fs.stream));
+    const int r = aov_launches(fs, prm, &dev, &events);
+    if (r == RT_OK) RT_HIP(hipEventRecord(fs.ev1, fs.stream));
+    return r;
+  };
+  const auto collect = [&]() -> int {
     // wait launch by launch: a fault surfaces after the launch it happened in
-    for (hipEvent_t ev : events)
-      if (r == RT_OK && e == hipSuccess) e = hipEventSynchronize(ev);
-    if (r == RT_OK && e == hipSuccess) e = hipEventSynchronize(fs.ev1);
+    for (hipEvent_t ev : events) RT_HIP(hipEventSynchronize(ev));
+    RT_HIP(hipEventSynchronize(fs.ev1));
     float ms = 0.0f;
-    if (r == RT_OK && e == hipSuccess) e = hipEventElapsedTime(&ms, fs.ev0, fs.ev1);
-    for (int k = 0; k < 6 && r == RT_OK && e == hipSuccess; ++k)
-      if (hp[k]) e = hipMemcpy(hp[k], d + off[k], bytes[k], hipMemcpyDeviceToHost);
-    if (!ok) (void)hipStreamSynchronize(fs.stream);  // launches may still write the buffers
-    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-    (void)hipFree(d);
-    if (r == RT_OK && e == hipSuccess && kernel_ms) *kernel_ms = ms;
-  }
-  if (r == RT_OK && e != hipSuccess) return hip_fail(e);
+    RT_HIP(hipEventElapsedTime(&ms, fs.ev0, fs.ev1));
+    for (int k = 0; k < 6; ++k)
+      if (hp[k]) RT_HIP(hipMemcpy(hp[k], stage.at<char>(off[k]), bytes[k], hipMemcpyDeviceToHost));
+    if (kernel_ms) *kernel_ms = ms;
+    return RT_OK;
+  };
+  int r = ps.end(enqueue());
+  if (r == RT_OK)
+    r = collect();
+  else
+    (void)hipStreamSynchronize(fs.stream);  // launches may still write the buffers
+  for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
   return r;
 }
 

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <limits>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "rt_internal.h"
@@ -23,15 +24,13 @@
 #include "rt_frame.h"
 #include "rt_layout.h"
 
-extern "C" void rt_internal_set_hip_error(int e);
 extern "C" hipError_t rt_internal_block_order(const uint32_t *tile_cost, uint32_t blocks, uint32_t units,
                                               uint32_t *order, hipStream_t st);
 
 // ------------------------------------------------------------ context ----
-struct rt_context {
-  int device = -1;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+// Everything that belongs to the uploaded scene: rt_scene_upload fills one and
+// moves it into the context, free_scene frees what it owns and starts afresh.
+struct scene_state {
   rtk::pair_geom *d_geom = nullptr;      // brute-force order
   rtk::pair_geom *d_bvh_geom = nullptr;  // BVH leaf order
   rtk::bvh_node *d_nodes = nullptr;
@@ -44,20 +43,28 @@ struct rt_context {
   uint32_t extra_pair0 = 0, n_extra_pairs = 0;
   uint32_t *d_grid_cells = nullptr;  // layer grid (nullptr: none)
   float *d_grid_items = nullptr;
+  size_t cells_cap = 0, items_cap = 0;  // d_grid_cells / d_grid_items capacity (u32 / items)
   size_t grid_n_items = 0;
   int grid_placement = rtk::kGridGlobal;  // rtk::kGrid*: where a launch keeps the grid
-  float grid_x0 = 0, grid_z0 = 0, grid_xi = 0, grid_zi = 0, grid_x1 = 0, grid_z1 = 0, grid_g = 0;
-  int grid_nx = 0, grid_nz = 0;
-  double grid_scale = 1.0;
+  rtk::grid_dims grid;                    // of the grid in the buffers (scale NaN: of neither, after a failed copy)
+  // the scene's largest lambertian / metal albedo: above 1, 64-bit pixel sums
+  // (sum_format), with a 64-bit scratch frame for atomic renders
+  double max_albedo = 0.0;
   // the layer grid's cell size fitted per frame geometry (rtk::grid_fitter,
   // DESIGN.md 3.3): the fitter, the geometry its grid was fitted for, and the
-  // host copy the last refit uploads from (ev_fit: after that copy)
+  // host copy the last refit uploads from (the context's ev_fit: after that copy)
   rtk::grid_fitter *fitter = nullptr;
   std::vector<uint64_t> fit_key;
   rtk::grid_geom fit_grid;
-  size_t cells_cap = 0, items_cap = 0;  // d_grid_cells / d_grid_items capacity (u32 / items)
-  hipEvent_t ev_fit = nullptr;
   bool fit_pending = false;
+};
+
+struct rt_context {
+  int device = -1;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  scene_state sc;
+  hipEvent_t ev_fit = nullptr;
   bool grid_fit = true;         // RT_OPT_GRID_FIT
   bool grid_scale_set = false;  // RT_OPT_GRID_SCALE given: no fitting
   unsigned long long *d_counters = nullptr;
@@ -86,10 +93,7 @@ struct rt_context {
   float tonemap_thr32[257];
   double *d_thr64 = nullptr;
   float *d_thr32 = nullptr;
-  // the scene's largest lambertian / metal albedo: above 1, 64-bit pixel sums
-  // (sum_format), with a 64-bit scratch frame for atomic renders
-  double max_albedo = 0.0;
-  uint64_t *d_wide = nullptr;
+  uint64_t *d_wide = nullptr;  // 64-bit scratch frame (sc.max_albedo above 1, atomic renders)
   size_t wide_n = 0;
   // rt_context_set_option
   rtk::accel_options opt;
@@ -98,10 +102,8 @@ struct rt_context {
 
 namespace {
 
-int hip_fail(hipError_t e) {
-  rt_internal_set_hip_error((int)e);
-  return RT_ERR_HIP;
-}
+// RT_OPT_GRID_PLACEMENT's values (0 = auto) as the builder's
+constexpr int kPlacementOpt[4] = {-1, rtk::kGridLds, rtk::kGridCells, rtk::kGridGlobal};
 
 // T[k] = the smallest q >= 0 whose correctly rounded square root reaches
 // k / 256 (k = 1..255; T[0] unused), in fp64 and in fp32.  (k / 256)^2 is
@@ -123,12 +125,6 @@ void tonemap_thresholds(double *t64, float *t32) {
   t32[256] = INFINITY;
 }
 
-#define RT_HIP(call)                         \
-  do {                                       \
-    hipError_t _e = (call);                  \
-    if (_e != hipSuccess) return hip_fail(_e); \
-  } while (0)
-
 bool params_ok(const rt_params *p) {
   return p && p->width >= 1 && p->height >= 1 && p->spp >= 0 && p->spp < (1 << 24) &&
          p->max_depth >= 0 && p->max_depth < (1 << 24) &&
@@ -137,32 +133,24 @@ bool params_ok(const rt_params *p) {
          (uint64_t)p->width * (uint64_t)p->height < (1ull << 32);
 }
 
+// frees what the record owns; it is then a fresh one
+void release(scene_state &s) {
+  for (void *d : {(void *)s.d_geom, (void *)s.d_bvh_geom, (void *)s.d_nodes, (void *)s.d_orig, (void *)s.d_shade,
+                  (void *)s.d_grid_cells, (void *)s.d_grid_items})
+    (void)hipFree(d);
+  delete s.fitter;
+  s = scene_state{};
+}
+
 void free_scene(rt_context *c) {
-  (void)hipFree(c->d_geom);
-  (void)hipFree(c->d_bvh_geom);
-  (void)hipFree(c->d_nodes);
-  (void)hipFree(c->d_orig);
-  (void)hipFree(c->d_shade);
-  (void)hipFree(c->d_grid_cells);
-  (void)hipFree(c->d_grid_items);
-  delete c->fitter;
-  c->fitter = nullptr;
-  c->fit_key.clear();
-  c->cells_cap = c->items_cap = 0;
-  c->d_grid_cells = nullptr;
-  c->d_grid_items = nullptr;
-  c->grid_nx = c->grid_nz = 0;
-  c->grid_n_items = 0;
-  c->grid_placement = rtk::kGridGlobal;
-  c->d_geom = c->d_bvh_geom = nullptr;
-  c->d_nodes = nullptr;
-  c->d_orig = nullptr;
-  c->d_shade = nullptr;
-  c->n_spheres = c->n_pad = c->n_nodes = c->n_bvh_slots = 0;
-  c->layer_mode = false;
-  c->extra_pair0 = c->n_extra_pairs = 0;
+  release(c->sc);
   c->order_key.clear();  // the pilot's tile costs belong to the old scene
-  c->max_albedo = 0.0;
+}
+
+// key += the camera's words
+void append_camera(std::vector<uint64_t> &key, const rt_camera *cam) {
+  const uint32_t *cw = reinterpret_cast<const uint32_t *>(cam);
+  for (size_t k = 0; k < sizeof(rt_camera) / 4; ++k) key.push_back(cw[k]);
 }
 
 template <class T>
@@ -286,12 +274,10 @@ int rt_context_set_option(rt_context *c, int option, double v) {
   if (!c || !std::isfinite(v)) return RT_ERR_INVALID;
   const bool dflt = v == 0.0;
   switch (option) {
-    case RT_OPT_GRID_PLACEMENT: {
-      static const int kMap[4] = {-1, rtk::kGridLds, rtk::kGridCells, rtk::kGridGlobal};
+    case RT_OPT_GRID_PLACEMENT:
       if (v != std::floor(v) || v < 0 || v > 3) return RT_ERR_INVALID;
-      c->opt.grid_placement = kMap[(int)v];
+      c->opt.grid_placement = kPlacementOpt[(int)v];
       return RT_OK;
-    }
     case RT_OPT_GRID_SCALE:
       if (!dflt && !(v >= 0.05 && v <= 20.0)) return RT_ERR_INVALID;
       c->opt.grid_scale = dflt ? 1.0 : v;
@@ -332,63 +318,51 @@ int rt_scene_upload(rt_context *c, const rt_scene_view *s) {
   rtk::accel_build a;
   rtk::accel_options o = c->opt;
   o.wide = rtk::max_albedo(s) > 1.0;
-  rtk::grid_fitter *fitter = nullptr;
-  rtk::build_accel(s, o, a, c->grid_fit && !c->grid_scale_set ? &fitter : nullptr);
+  scene_state sc;  // becomes the context's once its copies have completed
+  rtk::build_accel(s, o, a, c->grid_fit && !c->grid_scale_set ? &sc.fitter : nullptr);
+  sc.n_spheres = a.n;
+  sc.max_albedo = rtk::max_albedo(s);
+  sc.n_pad = a.n_pad;
+  sc.n_nodes = (uint32_t)a.per_order;  // nodes holds 8 orders of this many
+  sc.n_bvh_slots = (uint32_t)a.slots.size();
+  sc.oref2 = (float)(0.99 * a.oref * a.oref);
+  sc.layer_mode = a.layer_mode;
+  sc.layer_lo = a.layer_lo;
+  sc.layer_cy = a.layer_cy;
+  sc.layer_hi = a.layer_hi;
+  sc.extra_pair0 = a.extra_pair0;
+  sc.n_extra_pairs = a.n_extra_pairs;
+  sc.grid = a.grid;
 
-  RT_HIP(hipSetDevice(c->device));
   // renders enqueued on caller streams may still read the old scene: they
   // are serialised and each ends by recording ev_done, so the last one's
   // event covers them all (this context's work only, not the whole device)
-  {
-    hipError_t e0 = c->have_done ? hipEventSynchronize(c->ev_done) : hipSuccess;
-    if (e0 == hipSuccess) e0 = hipStreamSynchronize(c->stream);
-    if (e0 != hipSuccess) {
-      delete fitter;
-      return hip_fail(e0);
-    }
-  }
-  free_scene(c);
-  c->fitter = fitter;
-  hipError_t e = upload_vec(&c->d_geom, a.scan_geom, c->stream);
-  if (e == hipSuccess) e = upload_vec(&c->d_bvh_geom, a.bvh_geom, c->stream);
-  if (e == hipSuccess) e = upload_vec(&c->d_nodes, a.nodes, c->stream);
-  if (e == hipSuccess) e = upload_vec(&c->d_orig, a.slots, c->stream);
-  if (e == hipSuccess) e = upload_vec(&c->d_shade, a.shade, c->stream);
-  if (e == hipSuccess && !a.grid_cells.empty()) {
-    e = upload_vec(&c->d_grid_cells, a.grid_cells, c->stream);
-    if (e == hipSuccess) e = upload_vec(&c->d_grid_items, a.grid_items, c->stream);
-    c->cells_cap = a.grid_cells.size();
-    c->items_cap = a.grid_items.size() / 4;
-    c->grid_n_items = a.grid_items.size() / 4;
-    c->grid_placement = a.grid_placement;
-  }
+  hipError_t e = hipSetDevice(c->device);
+  if (e == hipSuccess && c->have_done) e = hipEventSynchronize(c->ev_done);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    free_scene(c);
+  if (e != hipSuccess) {  // (the old scene stays)
+    release(sc);
     return hip_fail(e);
   }
-  c->n_spheres = a.n;
-  c->max_albedo = rtk::max_albedo(s);
-  c->n_pad = a.n_pad;
-  c->n_nodes = (uint32_t)a.per_order;  // nodes holds 8 orders of this many
-  c->n_bvh_slots = (uint32_t)a.slots.size();
-  c->oref2 = (float)(0.99 * a.oref * a.oref);
-  c->layer_mode = a.layer_mode;
-  c->layer_lo = a.layer_lo;
-  c->layer_cy = a.layer_cy;
-  c->layer_hi = a.layer_hi;
-  c->extra_pair0 = a.extra_pair0;
-  c->n_extra_pairs = a.n_extra_pairs;
-  c->grid_x0 = a.grid_x0;
-  c->grid_xi = a.grid_xi;
-  c->grid_zi = a.grid_zi;
-  c->grid_z0 = a.grid_z0;
-  c->grid_x1 = a.grid_x1;
-  c->grid_z1 = a.grid_z1;
-  c->grid_g = a.grid_g;
-  c->grid_nx = a.grid_nx;
-  c->grid_nz = a.grid_nz;
-  c->grid_scale = a.grid_scale;
+  free_scene(c);
+  e = upload_vec(&sc.d_geom, a.scan_geom, c->stream);
+  if (e == hipSuccess) e = upload_vec(&sc.d_bvh_geom, a.bvh_geom, c->stream);
+  if (e == hipSuccess) e = upload_vec(&sc.d_nodes, a.nodes, c->stream);
+  if (e == hipSuccess) e = upload_vec(&sc.d_orig, a.slots, c->stream);
+  if (e == hipSuccess) e = upload_vec(&sc.d_shade, a.shade, c->stream);
+  if (e == hipSuccess && !a.grid.cells.empty()) {
+    e = upload_vec(&sc.d_grid_cells, a.grid.cells, c->stream);
+    if (e == hipSuccess) e = upload_vec(&sc.d_grid_items, a.grid.items, c->stream);
+    sc.cells_cap = a.grid.cells.size();
+    sc.items_cap = sc.grid_n_items = a.grid.items.size() / 4;
+    sc.grid_placement = a.grid_placement;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {  // (no scene)
+    release(sc);
+    return hip_fail(e);
+  }
+  c->sc = std::move(sc);
   return RT_OK;
 }
 
@@ -409,22 +383,24 @@ uint64_t valid_rows(const rt_params *prm) {
   return n;
 }
 
-// the kernel arguments of the context's current layer grid
-void grid_kparams(const rt_context *c, rtk::kparams &kp) {
-  kp.grid_cells = c->d_grid_cells;
-  kp.grid_items = (const rtk::f4 *)c->d_grid_items;
-  kp.grid_n_items = (int)c->grid_n_items;
-  kp.grid_n_cells = c->grid_nx * c->grid_nz;
-  kp.grid_x0 = c->grid_x0;
-  kp.grid_xi = c->grid_xi;
-  kp.grid_zi = c->grid_zi;
-  kp.grid_z0 = c->grid_z0;
-  kp.grid_x1 = c->grid_x1;
-  kp.grid_z1 = c->grid_z1;
-  kp.grid_g = c->grid_g;
-  kp.grid_invg = c->grid_g > 0.0f ? 1.0f / c->grid_g : 0.0f;
-  kp.grid_nx = c->grid_nx;
-  kp.grid_nz = c->grid_nz;
+// the kernel arguments of a layer grid in device memory (the one place that
+// knows both spellings of its geometry, rtk::grid_dims' and rtk::kparams')
+void grid_kparams(const rtk::grid_dims &g, const uint32_t *d_cells, const float *d_items, size_t n_items,
+                  rtk::kparams &kp) {
+  kp.grid_cells = d_cells;
+  kp.grid_items = (const rtk::f4 *)d_items;
+  kp.grid_n_items = (int)n_items;
+  kp.grid_n_cells = g.nx * g.nz;
+  kp.grid_x0 = g.x0;
+  kp.grid_xi = g.xi;
+  kp.grid_zi = g.zi;
+  kp.grid_z0 = g.z0;
+  kp.grid_x1 = g.x1;
+  kp.grid_z1 = g.z1;
+  kp.grid_g = g.g;
+  kp.grid_invg = g.g > 0.0f ? 1.0f / g.g : 0.0f;
+  kp.grid_nx = g.nx;
+  kp.grid_nz = g.nz;
 }
 
 // The kernel arguments of a render of (cam, prm) into accum_rgb with the
@@ -444,26 +420,27 @@ void fill_kparams(const rt_context *c, const rt_camera *cam, const rt_params *pr
   kp.band_offset = prm->band_offset;
   kp.local_rows = prm->local_rows;
   kp.tiles_x = (prm->width + rtk::kTile - 1) / rtk::kTile;
-  kp.n_pad = (int)c->n_pad;
-  kp.n_nodes = (int)c->n_nodes;
-  kp.oref2 = c->oref2;
-  kp.layer = rtk::f2{c->layer_lo, c->layer_hi};
-  kp.layer_mode = c->layer_mode ? 1 : 0;
-  kp.layer_cy = c->layer_cy;
-  kp.extra_pair0 = (int)c->extra_pair0;
-  kp.n_extra_pairs = (int)c->n_extra_pairs;
-  grid_kparams(c, kp);
+  const scene_state &s = c->sc;
+  kp.n_pad = (int)s.n_pad;
+  kp.n_nodes = (int)s.n_nodes;
+  kp.oref2 = s.oref2;
+  kp.layer = rtk::f2{s.layer_lo, s.layer_hi};
+  kp.layer_mode = s.layer_mode ? 1 : 0;
+  kp.layer_cy = s.layer_cy;
+  kp.extra_pair0 = (int)s.extra_pair0;
+  kp.n_extra_pairs = (int)s.n_extra_pairs;
+  grid_kparams(s.grid, s.d_grid_cells, s.d_grid_items, s.grid_n_items, kp);
   kp.seed32 = (uint32_t)prm->seed ^ ((uint32_t)(prm->seed >> 32) * 0x9E3779B9u);
   kp.flags = prm->flags;
   kp.inv_wm1 = (float)(1.0 / (prm->width - 1));
   kp.inv_hm1 = (float)(1.0 / (prm->height - 1));
-  kp.scan_geom = c->d_geom;
-  kp.geom = c->d_bvh_geom;
-  kp.nodes = c->d_nodes;
-  kp.orig = c->d_orig;
-  kp.extra_geom = c->d_bvh_geom ? c->d_bvh_geom + c->extra_pair0 : nullptr;
-  kp.extra_orig = c->d_orig ? c->d_orig + 2 * (size_t)c->extra_pair0 : nullptr;
-  kp.shade = c->d_shade;
+  kp.scan_geom = s.d_geom;
+  kp.geom = s.d_bvh_geom;
+  kp.nodes = s.d_nodes;
+  kp.orig = s.d_orig;
+  kp.extra_geom = s.d_bvh_geom ? s.d_bvh_geom + s.extra_pair0 : nullptr;
+  kp.extra_orig = s.d_orig ? s.d_orig + 2 * (size_t)s.extra_pair0 : nullptr;
+  kp.shade = s.d_shade;
   kp.out = accum_rgb;
   kp.counters = c->d_counters;
   {
@@ -481,8 +458,8 @@ void fill_kparams(const rt_context *c, const rt_camera *cam, const rt_params *pr
 
 // render_kernel variant bits of a render (rt_layout.h kVar*)
 int render_variant(const rt_context *c, const rt_params *prm, bool wide) {
-  const bool grid = c->d_grid_cells && !(prm->flags & RT_FLAG_LAYER_BVH);
-  const int place = grid ? c->grid_placement : rtk::kGridGlobal;
+  const bool grid = c->sc.d_grid_cells && !(prm->flags & RT_FLAG_LAYER_BVH);
+  const int place = grid ? c->sc.grid_placement : rtk::kGridGlobal;
   return (wide ? rtk::kVarWide : 0) | ((prm->flags & RT_FLAG_OPEN_INTERVAL) ? rtk::kVarOpen : 0) |
          ((prm->flags & RT_FLAG_METAL_UNIT_VECTOR) ? rtk::kVarMetalUnit : 0) |
          ((prm->flags & RT_FLAG_ACCEL_BVH) ? rtk::kVarBvh : 0) |
@@ -490,18 +467,13 @@ int render_variant(const rt_context *c, const rt_params *prm, bool wide) {
          (place << rtk::kVarPlaceShift);
 }
 
-// rt_render_async's body.  ev_start (may be null) is recorded on the stream
-// just before the render kernel itself, after any one-time setup (the pilot,
-// buffer growth), so that rt_render's kernel_ms times the render alone.
 // How a render is cut into launches (render_enqueue; rt_internal_launch_plan
 // shows it on the host).
 struct launch_plan {
   long long units, ranges, chunks, entries;
 };
 launch_plan plan_launches(const rt_params *prm, double launch_samples) {
-  const long long tiles_x = (prm->width + rtk::kTile - 1) / rtk::kTile;
-  const long long tiles = tiles_x * ((prm->local_rows + rtk::kTile - 1) / rtk::kTile);
-  const long long blocks = (tiles + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock;
+  const long long tiles = rt_frame_tiles(prm), blocks = rt_frame_blocks(prm);
   const bool traced = prm->spp > 0 && prm->max_depth > 0;
   const double frame_px = (double)prm->width * (double)prm->local_rows;
   const double total = traced ? frame_px * prm->spp : 0.0;
@@ -587,28 +559,28 @@ int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipSt
   if (prm->width == 0 || prm->local_rows == 0) return RT_OK;  // nothing to launch
   rtk::kparams &kp = fs.kp;
   fill_kparams(c, cam, prm, nullptr, kp);
-  const bool grid = c->d_grid_cells && !(prm->flags & RT_FLAG_LAYER_BVH);
-  if (grid && c->fitter && (prm->flags & RT_FLAG_ACCEL_BVH)) {
+  scene_state &s = c->sc;
+  const bool grid = s.d_grid_cells && !(prm->flags & RT_FLAG_LAYER_BVH);
+  if (grid && s.fitter && (prm->flags & RT_FLAG_ACCEL_BVH)) {
     // the layer grid's cell size for this frame geometry (rtk::grid_fitter:
     // a host-side model, once per geometry; the image is the same for every
     // size).  The new grid is copied into the context's buffers on st, after
     // every earlier render (renders of one context are serialised).
     std::vector<uint64_t> key = {(uint64_t)prm->width, (uint64_t)prm->height};
-    const uint32_t *cw = reinterpret_cast<const uint32_t *>(cam);
-    for (size_t k = 0; k < sizeof(rt_camera) / 4; ++k) key.push_back(cw[k]);
-    if (key != c->fit_key) {
-      const double scale = c->fitter->choose(*cam, prm->width, prm->height, nullptr);
-      if (scale != c->grid_scale) {
-        if (c->fit_pending) RT_HIP(hipEventSynchronize(c->ev_fit));  // fit_grid is still being read
-        c->fit_pending = false;
-        rtk::grid_geom &q = c->fit_grid;
-        if (!c->fitter->build(scale, q)) return RT_ERR_INVALID;  // (every candidate fits: unreachable)
+    append_camera(key, cam);
+    if (key != s.fit_key) {
+      const double scale = s.fitter->choose(*cam, prm->width, prm->height, nullptr);
+      if (scale != s.grid.scale) {
+        if (s.fit_pending) RT_HIP(hipEventSynchronize(c->ev_fit));  // fit_grid is still being read
+        s.fit_pending = false;
+        rtk::grid_geom &q = s.fit_grid;
+        if (!s.fitter->build(scale, q)) return RT_ERR_INVALID;  // (every candidate fits: unreachable)
         // Transactional: larger buffers are allocated before the
         // old ones are freed, so a failed allocation leaves the old grid whole
         // (buffers, fields and fit_key describe it); once a copy into the
         // buffers has failed they hold neither grid, and grid_scale = NaN makes
         // the next grid render refit before it launches.
-        if (q.cells.size() > c->cells_cap || q.items.size() / 4 > c->items_cap) {
+        if (q.cells.size() > s.cells_cap || q.items.size() / 4 > s.items_cap) {
           void *nc = nullptr, *ni = nullptr;
           hipError_t ea = hipMalloc(&nc, q.cells.size() * sizeof(uint32_t));
           if (ea == hipSuccess) ea = hipMalloc(&ni, q.items.size() * sizeof(float));
@@ -618,59 +590,48 @@ int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipSt
             (void)hipFree(ni);
             return hip_fail(ea);
           }
-          (void)hipFree(c->d_grid_cells);
-          (void)hipFree(c->d_grid_items);
-          c->d_grid_cells = static_cast<uint32_t *>(nc);
-          c->d_grid_items = static_cast<float *>(ni);
-          c->cells_cap = q.cells.size();
-          c->items_cap = q.items.size() / 4;
+          (void)hipFree(s.d_grid_cells);
+          (void)hipFree(s.d_grid_items);
+          s.d_grid_cells = static_cast<uint32_t *>(nc);
+          s.d_grid_items = static_cast<float *>(ni);
+          s.cells_cap = q.cells.size();
+          s.items_cap = q.items.size() / 4;
         }
-        c->grid_scale = std::numeric_limits<double>::quiet_NaN();
-        c->fit_key.clear();
-        RT_HIP(hipMemcpyAsync(c->d_grid_cells, q.cells.data(), q.cells.size() * sizeof(uint32_t),
+        s.grid.scale = std::numeric_limits<double>::quiet_NaN();
+        s.fit_key.clear();
+        RT_HIP(hipMemcpyAsync(s.d_grid_cells, q.cells.data(), q.cells.size() * sizeof(uint32_t),
                               hipMemcpyHostToDevice, st));
-        RT_HIP(hipMemcpyAsync(c->d_grid_items, q.items.data(), q.items.size() * sizeof(float), hipMemcpyHostToDevice,
+        RT_HIP(hipMemcpyAsync(s.d_grid_items, q.items.data(), q.items.size() * sizeof(float), hipMemcpyHostToDevice,
                               st));
         if (!c->ev_fit) RT_HIP(hipEventCreateWithFlags(&c->ev_fit, hipEventDisableTiming));
         RT_HIP(hipEventRecord(c->ev_fit, st));
-        c->fit_pending = true;
-        c->grid_n_items = q.items.size() / 4;
-        c->grid_x0 = q.x0;
-        c->grid_z0 = q.z0;
-        c->grid_xi = q.xi;
-        c->grid_zi = q.zi;
-        c->grid_x1 = q.x1;
-        c->grid_z1 = q.z1;
-        c->grid_g = q.g;
-        c->grid_nx = q.nx;
-        c->grid_nz = q.nz;
-        c->grid_scale = q.scale;
-        grid_kparams(c, kp);
+        s.fit_pending = true;
+        s.grid_n_items = q.items.size() / 4;
+        s.grid = q;
+        grid_kparams(s.grid, s.d_grid_cells, s.d_grid_items, s.grid_n_items, kp);
       }
-      c->fit_key = key;
+      s.fit_key = key;
     }
   }
   fs.grid = grid ? 1 : 0;
-  fs.placement = grid ? c->grid_placement : rtk::kGridGlobal;
+  fs.placement = grid ? s.grid_placement : rtk::kGridGlobal;
   fs.lds_bytes = rtk::grid_lds_bytes(fs.placement, kp.grid_n_items, kp.grid_n_cells);
   return RT_OK;
 }
 
-// ... and after them: ev_done on the pass's stream (rt_internal_frame_end)
-int frame_end(rt_context *c, hipStream_t st) {
-  RT_HIP(hipEventRecord(c->ev_done, st));
-  c->last_stream = st;
-  c->have_done = true;
-  return RT_OK;
-}
-
-int render_enqueue_body(rt_context *c, const rt_camera *cam, const rt_params *prm, float *accum_rgb, hipStream_t st,
-                        hipEvent_t ev_start) {
-  rt_frame_setup fs;
-  {
-    const int r = frame_begin(c, cam, prm, st, fs);
-    if (r != RT_OK) return r;
-  }
+// rt_render_async's body (stream NULL: the context's own).  ev_start (may be
+// null) is recorded on the stream just before the render kernel itself, after
+// any one-time setup (the pilot, buffer growth), so that rt_render's kernel_ms
+// times the render alone.  A render that fails after enqueuing some of its
+// work (a refit copy, the pilot, the k-th launch) still ends with ev_done
+// recorded behind that work (rt_pass_scope; ADVICE r5: before, only hipFree's
+// implicit device synchronisation covered it).
+int render_enqueue(rt_context *c, const rt_camera *cam, const rt_params *prm, float *accum_rgb, void *stream,
+                   hipEvent_t ev_start) {
+  rt_pass_scope ps(c, cam, prm, stream);
+  if (ps.status != RT_OK) return ps.status;
+  rt_frame_setup &fs = ps.fs;
+  const hipStream_t st = fs.stream;
   const uint64_t samples = (uint64_t)prm->width * valid_rows(prm) * (uint64_t)prm->spp;
   if (prm->flags & RT_FLAG_KEEP_COUNTERS) {
     c->last_samples += samples;
@@ -688,10 +649,8 @@ int render_enqueue_body(rt_context *c, const rt_camera *cam, const rt_params *pr
 
   rtk::kparams &kp = fs.kp;
   kp.out = accum_rgb;
-  const int tiles_y = (prm->local_rows + rtk::kTile - 1) / rtk::kTile;
-  const long long tiles = (long long)kp.tiles_x * tiles_y;
-  const unsigned blocks = (unsigned)((tiles + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock);
-  const sum_fmt fmt = sum_format(prm->spp, prm->max_depth, c->max_albedo);
+  const unsigned blocks = (unsigned)rt_frame_blocks(prm);
+  const sum_fmt fmt = sum_format(prm->spp, prm->max_depth, c->sc.max_albedo);
   const int v = render_variant(c, prm, fmt.wide);
   const size_t lds = fs.lds_bytes;
   const bool traced = prm->spp > 0 && prm->max_depth > 0;
@@ -722,8 +681,7 @@ int render_enqueue_body(rt_context *c, const rt_camera *cam, const rt_params *pr
     std::vector<uint64_t> key = {(uint64_t)prm->width, (uint64_t)prm->height, (uint64_t)prm->local_rows,
                                  (uint64_t)prm->row_block, (uint64_t)prm->band_stride,
                                  (uint64_t)prm->band_offset, (uint64_t)units, (uint64_t)(prm->flags & 0x12ffu)};
-    const uint32_t *cw = reinterpret_cast<const uint32_t *>(cam);
-    for (size_t k = 0; k < sizeof(rt_camera) / 4; ++k) key.push_back(cw[k]);
+    append_camera(key, cam);
     if (key != c->order_key || c->order_n != (size_t)blocks * units) {
       c->order_key.clear();  // valid again only once the new order is enqueued
       // tile costs, then 8 scratch counters (the context's are not touched)
@@ -806,19 +764,7 @@ int render_enqueue_body(rt_context *c, const rt_camera *cam, const rt_params *pr
     RT_HIP(rtk::launch_finish_sums_wide(c->d_wide, accum_rgb, frame_floats, kp.qinv, st));
   else if (kp.sum_atomic)
     RT_HIP(rtk::launch_finish_sums(reinterpret_cast<uint32_t *>(accum_rgb), frame_floats, kp.qinv, st));
-  return frame_end(c, st);
-}
-
-// A render that fails after enqueuing some of its work on st (a refit copy,
-// the pilot, the k-th launch) still ends with ev_done recorded on st, so that
-// the next render on another stream, and rt_scene_upload before it frees the
-// scene, wait for that work too (before, only hipFree's implicit
-// device synchronisation covered it).
-int render_enqueue(rt_context *c, const rt_camera *cam, const rt_params *prm, float *accum_rgb, hipStream_t st,
-                   hipEvent_t ev_start) {
-  const int r = render_enqueue_body(c, cam, prm, accum_rgb, st, ev_start);
-  if (r != RT_OK && c->ev_done) (void)frame_end(c, st);
-  return r;
+  return ps.end(RT_OK);
 }
 
 // rt_render's frame buffer (only it uses d_frame, and it returns after its
@@ -841,7 +787,7 @@ int rt_internal_frame_check(const rt_context *c, const rt_camera *cam, const rt_
   if (!c || !cam || !params_ok(prm)) return RT_ERR_INVALID;
   if (cam->model != RT_CAMERA_CPU && cam->model != RT_CAMERA_GPU) return RT_ERR_INVALID;
   if (cam->model == RT_CAMERA_CPU && (prm->width < 2 || prm->height < 2)) return RT_ERR_INVALID;
-  if (!c->d_geom) return RT_ERR_NO_SCENE;
+  if (!c->sc.d_geom) return RT_ERR_NO_SCENE;
   return RT_OK;
 }
 
@@ -860,18 +806,17 @@ int rt_internal_pass_begin(rt_context *c, void *stream, rt_frame_setup *out) {
 
 int rt_internal_frame_end(rt_context *c, hipStream_t stream) {
   if (!c || !c->ev_done) return RT_ERR_INVALID;
-  return frame_end(c, stream);
+  RT_HIP(hipEventRecord(c->ev_done, stream));
+  c->last_stream = stream;
+  c->have_done = true;
+  return RT_OK;
 }
 
 int rt_render_async(rt_context *c, const rt_camera *cam, const rt_params *prm, float *accum_rgb,
                     void *stream) {
   if (!c || !cam || !params_ok(prm) || (!accum_rgb && prm->local_rows && prm->width))
     return RT_ERR_INVALID;
-  {
-    const int r = rt_internal_frame_check(c, cam, prm);
-    if (r != RT_OK) return r;
-  }
-  return render_enqueue(c, cam, prm, accum_rgb, stream ? (hipStream_t)stream : c->stream, nullptr);
+  return render_enqueue(c, cam, prm, accum_rgb, stream, nullptr);  // (rt_internal_frame_check first)
 }
 
 int rt_render_progress(rt_context *c, uint32_t *done, uint32_t *total) {
@@ -909,7 +854,7 @@ int rt_collect_stats(rt_context *c, rt_stats *stats) {
   stats->segments = h[0];
   stats->wave_steps = h[1];
   stats->samples = c->last_samples;
-  stats->bf_tests = h[0] * (uint64_t)c->n_spheres;
+  stats->bf_tests = h[0] * (uint64_t)c->sc.n_spheres;
   stats->sphere_tests = c->last_stats ? h[2] : 0;
   stats->box_tests = c->last_stats ? h[3] : 0;
   stats->box_hits = c->last_stats ? h[4] : 0;
@@ -922,14 +867,13 @@ int rt_collect_stats(rt_context *c, rt_stats *stats) {
 int rt_render(rt_context *c, const rt_camera *cam, const rt_params *prm, float *host_rgb,
               rt_stats *stats) {
   if (!c || !params_ok(prm) || (!host_rgb && prm->local_rows && prm->width)) return RT_ERR_INVALID;
+  int st = rt_internal_frame_check(c, cam, prm);
+  if (st != RT_OK) return st;
   const size_t nf = 3 * (size_t)prm->width * (size_t)prm->local_rows;
   RT_HIP(hipSetDevice(c->device));
   RT_HIP(ensure_frame(c, nf));
-  if (!cam || (cam->model != RT_CAMERA_CPU && cam->model != RT_CAMERA_GPU)) return RT_ERR_INVALID;
-  if (cam->model == RT_CAMERA_CPU && (prm->width < 2 || prm->height < 2)) return RT_ERR_INVALID;
-  if (!c->d_geom) return RT_ERR_NO_SCENE;
   // ev0 is recorded right before the render kernel (after a first-frame pilot)
-  int st = render_enqueue(c, cam, prm, c->d_frame, c->stream, c->ev0);
+  st = render_enqueue(c, cam, prm, c->d_frame, nullptr, c->ev0);
   const uint32_t n_launch = std::min<uint32_t>(c->enq_launches, (uint32_t)c->ev_launch.size());
   if (st != RT_OK) return st;
   RT_HIP(hipEventRecord(c->ev1, c->stream));
@@ -967,10 +911,9 @@ int rt_internal_accel_info(const rt_scene_view *s, int grid_placement, double gr
   if (!out || !rtk::scene_ok(s) || grid_placement < 0 || grid_placement > 3 ||
       !(grid_scale == 0.0 || (grid_scale >= 0.05 && grid_scale <= 20.0)))
     return RT_ERR_INVALID;
-  static const int kMap[4] = {-1, rtk::kGridLds, rtk::kGridCells, rtk::kGridGlobal};
   rtk::accel_options o;
   o.wide = rtk::max_albedo(s) > 1.0;
-  o.grid_placement = kMap[grid_placement];
+  o.grid_placement = kPlacementOpt[grid_placement];
   o.grid_scale = grid_scale == 0.0 ? 1.0 : grid_scale;
   rtk::accel_build a;
   rtk::build_accel(s, o, a);
@@ -981,9 +924,10 @@ int rt_internal_accel_info(const rt_scene_view *s, int grid_placement, double gr
   v[2] = a.layer_mode ? 1u : 0u;
   v[3] = a.extra_pair0;
   v[4] = a.n_extra_pairs;
-  v[5] = (uint64_t)a.grid_nx;
-  v[6] = (uint64_t)a.grid_nz;
-  const uint64_t items = a.grid_items.size() / 4, cells = a.grid_cells.size();
+  const rtk::grid_geom &g = a.grid;
+  v[5] = (uint64_t)g.nx;
+  v[6] = (uint64_t)g.nz;
+  const uint64_t items = g.items.size() / 4, cells = g.cells.size();
   v[7] = items;
   v[8] = cells ? rtk::grid_lds_bytes(a.grid_placement, (long long)items, (long long)cells) : 0u;
   v[9] = cells && a.grid_placement == rtk::kGridLds;
@@ -992,13 +936,13 @@ int rt_internal_accel_info(const rt_scene_view *s, int grid_placement, double gr
   uint64_t maxc = 0, listed = 0;
   bool start_ok = true, ring_ok = true;
   for (uint64_t i = 0; i < cells; ++i) {
-    const uint32_t first = a.grid_cells[i] >> 4, cnt = a.grid_cells[i] & 15u;
-    const uint64_t next = i + 1 < cells ? (a.grid_cells[i + 1] >> 4) : items;
+    const uint32_t first = g.cells[i] >> 4, cnt = g.cells[i] & 15u;
+    const uint64_t next = i + 1 < cells ? (g.cells[i + 1] >> 4) : items;
     start_ok = start_ok && first + cnt == next;
     maxc = std::max<uint64_t>(maxc, cnt);
     listed += cnt ? 1u : 0u;
-    const int x = (int)(i % a.grid_nx), z = (int)(i / a.grid_nx);
-    if (x == 0 || z == 0 || x == a.grid_nx - 1 || z == a.grid_nz - 1) ring_ok = ring_ok && cnt == 0;
+    const int x = (int)(i % g.nx), z = (int)(i / g.nx);
+    if (x == 0 || z == 0 || x == g.nx - 1 || z == g.nz - 1) ring_ok = ring_ok && cnt == 0;
   }
   v[10] = maxc;
   v[11] = cells ? (start_ok ? 1u : 0u) : 0u;
@@ -1008,7 +952,7 @@ int rt_internal_accel_info(const rt_scene_view *s, int grid_placement, double gr
   v[15] = listed;
   static const uint64_t kPlaceOut[3] = {RT_GRID_GLOBAL, RT_GRID_LDS, RT_GRID_CELLS_LDS};
   v[16] = cells ? kPlaceOut[a.grid_placement] : 0u;
-  v[17] = (uint64_t)std::llround(a.grid_scale * 1000.0);
+  v[17] = (uint64_t)std::llround(g.scale * 1000.0);
   std::memcpy(out, v, std::min<size_t>(n_out, RT_ACCEL_INFO_N) * sizeof(uint64_t));
   return RT_OK;
 }
@@ -1045,7 +989,7 @@ int rt_internal_grid_fit_phase(const rt_scene_view *s, const rt_camera *cam, int
 
 int rt_internal_grid_scale(rt_context *c, double *scale) {
   if (!c || !scale) return RT_ERR_INVALID;
-  *scale = c->d_grid_cells ? c->grid_scale : 0.0;
+  *scale = c->sc.d_grid_cells ? c->sc.grid.scale : 0.0;
   return RT_OK;
 }
 

@@ -26,8 +26,6 @@
 #include "rt_denoise.h"
 #include "rt_frame.h"
 
-extern "C" void rt_internal_set_hip_error(int e);
-
 namespace rtk {
 
 #define RT_GLOBAL __attribute__((address_space(1)))
@@ -190,17 +188,6 @@ __global__ __launch_bounds__(256) void atrous_kernel(const dn_params a) {
 
 namespace {
 
-int hip_fail(hipError_t e) {
-  rt_internal_set_hip_error((int)e);
-  return RT_ERR_HIP;
-}
-
-#define RT_HIP(call)                           \
-  do {                                         \
-    hipError_t _e = (call);                    \
-    if (_e != hipSuccess) return hip_fail(_e); \
-  } while (0)
-
 // the desc's options with the defaults filled in; false: out of range
 struct dn_options {
   int iterations, normal_power;
@@ -283,15 +270,8 @@ size_t rt_denoise_scratch_bytes(int width, int height) {
 int rt_denoise_async(rt_context *c, const rt_denoise_desc *d, void *scratch, void *stream) {
   dn_options o;
   if (!c || !d || !scratch || ((uintptr_t)scratch & 15) || !resolve(d, o)) return RT_ERR_INVALID;
-  rt_frame_setup fs;
-  std::memset(&fs, 0, sizeof fs);
-  int r = rt_internal_pass_begin(c, stream, &fs);
-  if (r == RT_OK) r = enqueue(d, o, scratch, fs.stream);
-  if (fs.stream) {
-    const int re = rt_internal_frame_end(c, fs.stream);
-    if (r == RT_OK) r = re;
-  }
-  return r;
+  rt_pass_scope ps(c, nullptr, nullptr, stream);
+  return ps.end(ps.status == RT_OK ? enqueue(d, o, scratch, ps.fs.stream) : ps.status);
 }
 
 int rt_denoise(rt_context *c, const rt_denoise_desc *host, double *kernel_ms) {
@@ -303,49 +283,40 @@ int rt_denoise(rt_context *c, const rt_denoise_desc *host, double *kernel_ms) {
   // albedo, then the scratch; every part 256-byte aligned
   const void *hp[5] = {host->beauty, host->hits, host->position, host->normal, host->albedo};
   const size_t bytes[5] = {12 * npx, 4 * npx, 12 * npx, 12 * npx, 12 * npx};
-  size_t off[6], total = 0;
-  for (int k = 0; k < 5; ++k) {
-    off[k] = total;
-    total += (bytes[k] + 255) / 256 * 256;
-  }
-  off[5] = total;
-  total += rt_denoise_scratch_bytes(host->width, host->height);
-  rt_frame_setup fs;
-  std::memset(&fs, 0, sizeof fs);
-  char *d = nullptr;
-  hipError_t e = hipSuccess;
-  int r = rt_internal_pass_begin(c, nullptr, &fs);  // (sets the device)
-  if (r == RT_OK) {
-    e = hipMalloc((void **)&d, total);
-    for (int k = 0; k < 5 && e == hipSuccess; ++k)
-      e = hipMemcpyAsync(d + off[k], hp[k], bytes[k], hipMemcpyHostToDevice, fs.stream);
-    if (e == hipSuccess) e = hipEventRecord(fs.ev0, fs.stream);
-    if (e == hipSuccess) {
-      rt_denoise_desc dev = *host;
-      dev.beauty = reinterpret_cast<const float *>(d + off[0]);
-      dev.hits = reinterpret_cast<const uint32_t *>(d + off[1]);
-      dev.position = reinterpret_cast<const float *>(d + off[2]);
-      dev.normal = reinterpret_cast<const float *>(d + off[3]);
-      dev.albedo = reinterpret_cast<const float *>(d + off[4]);
-      dev.out = reinterpret_cast<float *>(d + off[0]);
-      r = enqueue(&dev, o, d + off[5], fs.stream);
-    }
-    if (e == hipSuccess && r == RT_OK) e = hipEventRecord(fs.ev1, fs.stream);
-  }
+  rt_staging stage;
+  size_t off[6];
+  for (int k = 0; k < 5; ++k) off[k] = stage.add(bytes[k]);
+  off[5] = stage.add(rt_denoise_scratch_bytes(host->width, host->height));
+  rt_pass_scope ps(c, nullptr, nullptr, nullptr);  // (sets the device)
+  const rt_frame_setup &fs = ps.fs;
+  const auto run = [&]() -> int {
+    if (ps.status != RT_OK) return ps.status;
+    RT_HIP(stage.alloc());
+    for (int k = 0; k < 5; ++k)
+      RT_HIP(hipMemcpyAsync(stage.at<char>(off[k]), hp[k], bytes[k], hipMemcpyHostToDevice, fs.stream));
+    RT_HIP(hipEventRecord(fs.ev0, fs.stream));
+    rt_denoise_desc dev = *host;
+    dev.beauty = dev.out = stage.at<float>(off[0]);
+    dev.hits = stage.at<uint32_t>(off[1]);
+    dev.position = stage.at<float>(off[2]);
+    dev.normal = stage.at<float>(off[3]);
+    dev.albedo = stage.at<float>(off[4]);
+    const int r = enqueue(&dev, o, stage.at<char>(off[5]), fs.stream);
+    if (r == RT_OK) RT_HIP(hipEventRecord(fs.ev1, fs.stream));
+    return r;
+  };
+  int r = ps.end(run());
   if (fs.stream) {
-    const int re = rt_internal_frame_end(c, fs.stream);
-    if (r == RT_OK && e == hipSuccess) r = re;
     // whatever was enqueued reads the host arrays and the allocation: wait
     const hipError_t es = hipStreamSynchronize(fs.stream);
-    if (e == hipSuccess) e = es;
+    if (r == RT_OK && es != hipSuccess) r = hip_fail(es);
   }
+  if (r != RT_OK) return r;
   float ms = 0.0f;
-  if (r == RT_OK && e == hipSuccess) e = hipEventElapsedTime(&ms, fs.ev0, fs.ev1);
-  if (r == RT_OK && e == hipSuccess) e = hipMemcpy(host->out, d + off[0], bytes[0], hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (r == RT_OK && e == hipSuccess && kernel_ms) *kernel_ms = ms;
-  if (r == RT_OK && e != hipSuccess) return hip_fail(e);
-  return r;
+  RT_HIP(hipEventElapsedTime(&ms, fs.ev0, fs.ev1));
+  RT_HIP(hipMemcpy(host->out, stage.at<char>(off[0]), bytes[0], hipMemcpyDeviceToHost));
+  if (kernel_ms) *kernel_ms = ms;
+  return RT_OK;
 }
 
 }  // extern "C"

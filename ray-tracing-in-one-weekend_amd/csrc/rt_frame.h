@@ -1,12 +1,16 @@
 // rt_frame.h -- internal: how a pass over the context's scene (the render in
 // rt_api.cpp, the first-hit feature pass in rt_aov.hip / librtow_aov.so), or a
 // pass that only shares the context's ordering (the denoiser in
-// rt_denoise.hip / librtow_denoise.so), starts and ends on a stream.  Not installed; rt_context stays opaque outside
-// rt_api.cpp, so the second library gets what it needs through this struct.
+// rt_denoise.hip / librtow_denoise.so), starts and ends on a stream, and the
+// host helpers the three share (hip_fail / RT_HIP, rt_pass_scope, rt_staging).
+// Not installed; rt_context stays opaque outside rt_api.cpp, so the other
+// libraries get what they need through rt_frame_setup.
 #ifndef RTOW_RT_FRAME_H
 #define RTOW_RT_FRAME_H
 
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 #include "rt_layout.h"
 
@@ -21,6 +25,8 @@ struct rt_frame_setup {
 };
 
 extern "C" {
+
+void rt_internal_set_hip_error(int e);
 
 // The argument checks of rt_render_async without its buffer: RT_ERR_INVALID
 // or RT_ERR_NO_SCENE, else RT_OK.  No HIP call.
@@ -46,5 +52,76 @@ int rt_internal_pass_begin(rt_context *ctx, void *stream, rt_frame_setup *out);
 int rt_internal_frame_end(rt_context *ctx, hipStream_t stream);
 
 }  // extern "C"
+
+// A failed HIP call's status; rt_last_hip_error reports e
+inline int hip_fail(hipError_t e) {
+  rt_internal_set_hip_error((int)e);
+  return RT_ERR_HIP;
+}
+
+#define RT_HIP(call)                           \
+  do {                                         \
+    hipError_t _e = (call);                    \
+    if (_e != hipSuccess) return hip_fail(_e); \
+  } while (0)
+
+// The frame's 8x8 tiles (one wave each) and its blocks of kWavesPerBlock tiles
+inline long long rt_frame_tiles(const rt_params *prm) {
+  return (long long)((prm->width + rtk::kTile - 1) / rtk::kTile) * ((prm->local_rows + rtk::kTile - 1) / rtk::kTile);
+}
+inline long long rt_frame_blocks(const rt_params *prm) {
+  return (rt_frame_tiles(prm) + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock;
+}
+
+// One pass on a stream: begins it (cam NULL: rt_internal_pass_begin, else
+// rt_internal_frame_begin) and, exactly when the begin got as far as a stream,
+// ends it with rt_internal_frame_end -- in end(), or on leaving the scope: a
+// pass that fails after enqueuing some of its work still has ev_done recorded
+// behind that work, so that the context's next pass on another stream, and
+// rt_scene_upload before it frees the scene, wait for it too.
+struct rt_pass_scope {
+  rt_frame_setup fs;
+  int status;  // of the begin
+  rt_pass_scope(rt_context *c, const rt_camera *cam, const rt_params *prm, void *stream) : c_(c) {
+    std::memset(&fs, 0, sizeof fs);
+    status = cam ? rt_internal_frame_begin(c, cam, prm, stream, &fs) : rt_internal_pass_begin(c, stream, &fs);
+  }
+  rt_pass_scope(const rt_pass_scope &) = delete;
+  ~rt_pass_scope() { (void)end(RT_OK); }
+  // ends the pass; r, the status of its launches, with the end's folded in (the first error wins)
+  int end(int r) {
+    if (!fs.stream || ended_) return r;
+    ended_ = true;
+    const int re = rt_internal_frame_end(c_, fs.stream);
+    return r != RT_OK ? r : re;
+  }
+
+ private:
+  rt_context *c_;
+  bool ended_ = false;
+};
+
+// A synchronous wrapper's device buffers: 256-byte aligned parts of one
+// allocation, freed on leaving the scope.  add() the parts, alloc(), then at().
+class rt_staging {
+ public:
+  size_t add(size_t bytes) {
+    const size_t off = total_;
+    total_ += (bytes + 255) / 256 * 256;
+    return off;
+  }
+  hipError_t alloc() { return hipMalloc((void **)&d_, total_); }
+  template <class T>
+  T *at(size_t off) const {
+    return reinterpret_cast<T *>(d_ + off);
+  }
+  rt_staging() = default;
+  rt_staging(const rt_staging &) = delete;
+  ~rt_staging() { (void)hipFree(d_); }
+
+ private:
+  char *d_ = nullptr;
+  size_t total_ = 0;
+};
 
 #endif  // RTOW_RT_FRAME_H

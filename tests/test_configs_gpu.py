@@ -229,6 +229,30 @@ def test_grid_refit_between_async_renders_on_two_streams(rtow, oracle):
             assert ctx.collect_stats().segments == segs
 
 
+def test_scene_reupload_on_a_live_context(rtow, oracle):
+    """rt_scene_upload replaces the context's whole scene record: the final
+    scene rendered with camera A (which fits the grid), then the five-sphere
+    scene (no layer grid: grid_scale() == 0), then the final scene again with
+    a camera B whose fitted scale differs from A's (the refit test's pair) --
+    every image and segment count equals the oracle's, so nothing of a
+    replaced scene (grid geometry, fit key, counts) reaches a later render."""
+    W, H = 64, 36
+    final, five = rtow.final_scene(), rtow.five_scene()
+    cam_a = rtow.camera_cpu(aspect=W / H)
+    cam_b = rtow.camera_cpu(lookfrom=(6, 1, 12), aspect=W / H)
+    fit_a, fit_b = rtow.grid_fit(final, cam_a, W, H)[0], rtow.grid_fit(final, cam_b, W, H)[0]
+    assert fit_a != fit_b, (fit_a, fit_b)  # precondition: B's render needs another grid than A left
+    p = rtow.make_params(W, H, 8, seed=41, flags=GRID)
+    with rtow.Context(0) as ctx:
+        for scene, cam, fit in ((final, cam_a, fit_a), (five, cam_a, 0.0), (final, cam_b, fit_b)):
+            ctx.upload(scene)
+            got, st = ctx.render(cam, p)
+            assert ctx.grid_scale() == pytest.approx(fit, abs=1e-12)
+            want, segs = kernel_render(scene, cam, p)
+            assert np.array_equal(got, want)
+            assert st.segments == segs
+
+
 def test_pilot_first_render_is_asynchronous_and_correct(rtow):
     """The pilot schedule's first render of a geometry enqueues the pilot, the
     device sort and the render without a host sync; the result equals launch

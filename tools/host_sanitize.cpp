@@ -1,7 +1,8 @@
 // tools/host_sanitize.cpp -- drives the library's host code under ASan + UBSan
 // on the CPU (no device): the scene builders, both cameras, the BVH / layer-grid
-// builder (rt_internal_accel_info), both tonemaps and the P3 / P6 writers, on
-// the reference scenes and on ragged / degenerate inputs.  Built and run by
+// builder (rt_internal_accel_info) and its grid fitter (csrc/rt_accel.h, linked
+// directly), both tonemaps and the P3 / P6 writers, on the reference scenes
+// and on ragged / degenerate inputs.  Built and run by
 // tools/host_sanitize.sh; exits non-zero on any failed check (the sanitizers
 // abort on their own findings).
 #include <cmath>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "rt_internal.h"
+#include "rt_accel.h"
 
 #define CHECK(x)                                                    \
   do {                                                              \
@@ -49,6 +51,55 @@ static void accel(const rt_scene_view &v, bool expect_layer) {
   CHECK(rt_internal_accel_info(&v, 4, 0.0, two, 2) != RT_OK);
 }
 
+// what rt_internal_accel_info checks of a built grid: nx x nz stored cells,
+// whole items, running item starts, an empty ring
+static void grid_ok(const rtk::grid_geom &g) {
+  CHECK(g.nx >= 3 && g.nz >= 3 && g.cells.size() == (size_t)g.nx * (size_t)g.nz);
+  CHECK(g.items.size() % 4 == 0);
+  const size_t items = g.items.size() / 4;
+  for (size_t i = 0; i < g.cells.size(); ++i) {
+    const uint32_t first = g.cells[i] >> 4, cnt = g.cells[i] & 15u;
+    CHECK(first + cnt == (i + 1 < g.cells.size() ? g.cells[i + 1] >> 4 : items));
+    const int x = (int)(i % g.nx), z = (int)(i / g.nx);
+    if (x == 0 || z == 0 || x == g.nx - 1 || z == g.nz - 1) CHECK(cnt == 0);
+  }
+}
+
+// The grid fitter behind RT_OPT_GRID_FIT, for every requested placement that
+// can have one: each candidate scale that choose() reports for a camera builds
+// a sound grid, and build() at the builder's own scale reproduces the grid
+// build_accel returned (one rtk::grid_geom from the builder to the refit).
+static void fitter(const rt_scene_view &v, const rt_camera (&cams)[2]) {
+  for (int place : {-1, (int)rtk::kGridLds, (int)rtk::kGridCells}) {
+    rtk::accel_options o;
+    o.grid_placement = place;
+    rtk::accel_build a;
+    rtk::grid_fitter *f = nullptr;
+    rtk::build_accel(&v, o, a, &f);
+    CHECK(!a.grid.cells.empty());
+    grid_ok(a.grid);
+    CHECK((f != nullptr) == (a.grid_placement != rtk::kGridGlobal));
+    if (!f) continue;  // (10 000 spheres do not fit kGridLds: global memory, no fitter)
+    rtk::grid_geom g;
+    CHECK(f->build(a.grid.scale, g));
+    CHECK(g == a.grid);
+    for (const rt_camera &cam : cams) {
+      std::vector<std::pair<double, double>> cs;
+      const double best = f->choose(cam, 640, 360, &cs);
+      CHECK(!cs.empty() && cs.size() <= (size_t)rtk::kFitSteps + 1);
+      bool seen = false;
+      for (const std::pair<double, double> &c : cs) {
+        CHECK(f->build(c.first, g));
+        CHECK(g.scale == c.first);
+        grid_ok(g);
+        seen = seen || c.first == best;
+      }
+      CHECK(seen);
+    }
+    delete f;
+  }
+}
+
 int main() {
   // the final scene at several sizes (half extent 11: 486 spheres; 50: 10k)
   for (int he : {0, 1, 3, 11, 50}) {
@@ -70,6 +121,10 @@ int main() {
       CHECK(rt_internal_grid_fit(&v, &cam, 3840, 2160, &scale, costs, 40, &n) == RT_OK);
       CHECK(scale > 0 && n >= 1 && n <= 31);
       CHECK(rt_internal_grid_fit(&v, &cam, 64, 64, &scale, nullptr, 0, &n) == RT_OK);
+      rt_camera cams[2] = {cam, cam};
+      const double from2[3] = {-3, 6, 12};
+      CHECK(rt_camera_cpu(from2, at, up, 40.0, 1.0, 0.0, 10.0, &cams[1]) == RT_OK);
+      fitter(v, cams);
     }
   }
   {  // too small a buffer is refused

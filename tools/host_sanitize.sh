@@ -19,7 +19,7 @@ $HIPCC $FLAGS $HSAN -c -o $OUT/rt_api.o $PKG/csrc/rt_api.cpp
 $HIPCC $FLAGS $HSAN -c -o $OUT/rt_accel.o $PKG/csrc/rt_accel.cpp
 $HIPCC $FLAGS $HSAN -c -o $OUT/rt_sched.o $PKG/csrc/rt_sched.hip
 $HIPCC $FLAGS $HSAN -x c++ -c -o $OUT/rt_host.o $PKG/csrc/rt_host.cpp
-$HIPCC $FLAGS $HSAN -x c++ -c -o $OUT/driver.o $ROOT/tools/host_sanitize.cpp
+$HIPCC $FLAGS $HSAN -c -o $OUT/driver.o $ROOT/tools/host_sanitize.cpp  # (csrc/rt_accel.h needs the HIP headers)
 $HIPCC --offload-arch=gfx950 $HSAN -o $OUT/host_sanitize $OUT/driver.o $OUT/rt_host.o $OUT/rt_kernel.o $OUT/rt_api.o $OUT/rt_accel.o \
   $OUT/rt_sched.o -lpthread
 ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 $OUT/host_sanitize
