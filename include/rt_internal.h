@@ -45,8 +45,17 @@ int rt_device_kat(int device, int kind, const double *in, size_t n_cases, double
  *   8 grid LDS bytes        9 whole grid in LDS 10 max items/cell 11 start invariant
  *  12 empty ring cells ok  13 oref * 1000      14 layer slots    15 listed cells
  *  16 placement (RT_GRID_*, 0: no grid)         17 cell scale * 1000
+ *  18 class of the first extras group (RT_EXTRAS_* bits: it picks the grid
+ *     build's form of that group's test)        19 bits of the centre y its
+ *     coaxial spheres share (float32; 0 without RT_EXTRAS_COAXIAL)
+ *  20..35 the first 16 extras slots in scan order: 1 + original index (the
+ *     slot's tie key), 0 = padding or no such slot
+ * Classes compare bit patterns; only +0 is zero:
+ *   RT_EXTRAS_AXIAL    slot 0 has cx = cz = +0
+ *   RT_EXTRAS_COAXIAL  the group's other spheres share one cy and have cz = +0
  * For tests and sanitizer runs. */
-#define RT_ACCEL_INFO_N 18
+#define RT_ACCEL_INFO_N 36
+enum { RT_EXTRAS_AXIAL = 1, RT_EXTRAS_COAXIAL = 2 };
 int rt_internal_accel_info(const rt_scene_view *scene, int grid_placement, double grid_scale, uint64_t *out,
                            size_t n_out);
 

@@ -503,6 +503,43 @@ double max_albedo(const rt_scene_view *s) {
 }
 
 
+// The class of the first extras group (rt_layout.h kFold*; the grid build's
+// scan_extras drops the terms a class makes exact zeros or shares).  Decided on
+// bit patterns, because the folded test has to give the general test's bits:
+//  * a centre coordinate counts as zero only when it is +0.  (The bit argument
+//    in rt_device.h covers -0 as well -- the dropped product is then -+0
+//    instead of +-0 -- but a scene that spells a centre -0 gains nothing from
+//    the fold being stretched to it, and one exact pattern keeps the class a
+//    plain compare: -0, like 1e-30, takes the general form.)
+//  * the coaxial spheres share one centre-y bit pattern: the shared pair
+//    fma(cy, dy, nk1), fma(cy, oy2, o2) is then each sphere's own.
+// Padding slots (-1) are never candidates (ks = +inf) and do not count.
+int classify_extras(const rt_scene_view *s, const int *slots, size_t n_slots, float *cy) {
+  const auto bits = [](float x) {
+    uint32_t u;
+    std::memcpy(&u, &x, sizeof u);
+    return u;
+  };
+  if (cy) *cy = 0.0f;
+  if (n_slots < 4 || slots[0] < 0) return 0;
+  int cls = 0;
+  if (bits(s->cx[slots[0]]) == 0u && bits(s->cz[slots[0]]) == 0u) cls |= kFoldLead;
+  int n_rest = 0;
+  bool same = true;
+  float y = 0.0f;
+  for (int k = 1; k < 4; ++k) {
+    const int i = slots[k];
+    if (i < 0) continue;
+    if (!n_rest++) y = s->cy[i];
+    same = same && bits(s->cy[i]) == bits(y) && bits(s->cz[i]) == 0u;
+  }
+  if (n_rest && same) {
+    cls |= kFoldRest;
+    if (cy) *cy = y;
+  }
+  return cls;
+}
+
 void build_accel(const rt_scene_view *s, const accel_options &o, accel_build &a, grid_fitter **fitter) {
   if (fitter) *fitter = nullptr;
   const uint32_t n = s->n;
@@ -585,6 +622,9 @@ void build_accel(const rt_scene_view *s, const accel_options &o, accel_build &a,
   a.layer_cy = bb.layer_cy;
   a.extra_pair0 = bb.extra_pair0;
   a.n_extra_pairs = bb.n_extra_pairs;
+  if (a.layer_mode && a.n_extra_pairs)
+    a.extras_fold = classify_extras(s, a.slots.data() + 2 * (size_t)a.extra_pair0, 2 * (size_t)a.n_extra_pairs,
+                                    &a.extras_cy);
   a.grid = bb.grid;
   a.grid_placement = bb.grid.cells.empty() ? kGridGlobal : place;
   // the builder's layer split and boxes go on into the grid fitter

@@ -60,6 +60,8 @@ struct accel_build {
   bool layer_mode = false;
   float layer_lo = 0.0f, layer_hi = 0.0f, layer_cy = 0.0f;
   uint32_t extra_pair0 = 0, n_extra_pairs = 0;
+  int extras_fold = 0;     // kFold* bits of the first extras group (classify_extras)
+  float extras_cy = 0.0f;  // kFoldRest: the centre y its spheres share
   grid_geom grid;                        // layer grid (cells empty: none)
   int grid_placement = kGridGlobal;
 };
@@ -106,6 +108,11 @@ bool scene_ok(const rt_scene_view *s);
 double max_albedo(const rt_scene_view *s);
 // per sphere: 1 if the opaque-inside rule applies to it (sealed lambertian ball)
 void sealed_spheres(const rt_scene_view *s, std::vector<uint8_t> &out);
+// The class of a layer scene's first extras group, slots[0..4) of the extras
+// (original indices, -1 padding): kFold* bits, and with kFoldRest the shared
+// centre y in *cy.  Compares bit patterns: only +0 is zero (-0 is declined),
+// and "one centre y" means one bit pattern.
+int classify_extras(const rt_scene_view *s, const int *slots, size_t n_slots, float *cy);
 // fitter (may be null): a grid fitter for the scene's layer grid, when it sits
 // in an LDS placement (else null); the caller owns it
 void build_accel(const rt_scene_view *s, const accel_options &o, accel_build &out, grid_fitter **fitter = nullptr);

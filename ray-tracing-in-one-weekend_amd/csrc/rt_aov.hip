@@ -110,7 +110,19 @@ __global__ __launch_bounds__(kBlock) void aov_kernel(const aov_params a) {
       const float tmin = camera_ray(p, pcg4d(pix, (uint32_t)s, 0u, p.seed32), col, grow, ox, oy, oz, dx, dy, dz);
       float walked = 0.0f;  // distance to the current origin (0 unless a spurious root moved it)
       while (true) {
-        const hit_state hs = closest_hit<OPEN, BVH, false, GRID, GP>(ox, oy, oz, dx, dy, dz, tmin, wc);
+        // the render's choice of the first extras group's form (kparams
+        // extras_fold), taken here at run time: one kernel per walk, the
+        // class a wave-uniform branch
+        hit_state hs;
+        const int fold = GRID ? p.extras_fold : 0;
+        if (fold == (kFoldLead | kFoldRest))
+          hs = closest_hit<OPEN, BVH, false, GRID, GP, GRID ? kFoldLead | kFoldRest : 0>(ox, oy, oz, dx, dy, dz, tmin, wc);
+        else if (fold == kFoldLead)
+          hs = closest_hit<OPEN, BVH, false, GRID, GP, GRID ? kFoldLead : 0>(ox, oy, oz, dx, dy, dz, tmin, wc);
+        else if (fold == kFoldRest)
+          hs = closest_hit<OPEN, BVH, false, GRID, GP, GRID ? kFoldRest : 0>(ox, oy, oz, dx, dy, dz, tmin, wc);
+        else
+          hs = closest_hit<OPEN, BVH, false, GRID, GP, 0>(ox, oy, oz, dx, dy, dz, tmin, wc);
         const int best = best_of<OPEN>(hs);
         if (best < 0) break;  // a miss adds nothing
         // render_kernel's hit block for a camera ray (origin_sphere = -1)

@@ -41,6 +41,8 @@ struct scene_state {
   bool layer_mode = false;
   float layer_lo = 0.0f, layer_hi = 0.0f, layer_cy = 0.0f;
   uint32_t extra_pair0 = 0, n_extra_pairs = 0;
+  int extras_fold = 0;     // rtk::kFold* bits of the first extras group
+  float extras_cy = 0.0f;  // kFoldRest: the centre y its spheres share
   uint32_t *d_grid_cells = nullptr;  // layer grid (nullptr: none)
   float *d_grid_items = nullptr;
   size_t cells_cap = 0, items_cap = 0;  // d_grid_cells / d_grid_items capacity (u32 / items)
@@ -332,6 +334,8 @@ int rt_scene_upload(rt_context *c, const rt_scene_view *s) {
   sc.layer_hi = a.layer_hi;
   sc.extra_pair0 = a.extra_pair0;
   sc.n_extra_pairs = a.n_extra_pairs;
+  sc.extras_fold = a.extras_fold;
+  sc.extras_cy = a.extras_cy;
   sc.grid = a.grid;
 
   // renders enqueued on caller streams may still read the old scene: they
@@ -429,6 +433,8 @@ void fill_kparams(const rt_context *c, const rt_camera *cam, const rt_params *pr
   kp.layer_cy = s.layer_cy;
   kp.extra_pair0 = (int)s.extra_pair0;
   kp.n_extra_pairs = (int)s.n_extra_pairs;
+  kp.extras_fold = s.extras_fold;
+  kp.extras_cy = s.extras_cy;
   grid_kparams(s.grid, s.d_grid_cells, s.d_grid_items, s.grid_n_items, kp);
   kp.seed32 = (uint32_t)prm->seed ^ ((uint32_t)(prm->seed >> 32) * 0x9E3779B9u);
   kp.flags = prm->flags;
@@ -460,7 +466,9 @@ void fill_kparams(const rt_context *c, const rt_camera *cam, const rt_params *pr
 int render_variant(const rt_context *c, const rt_params *prm, bool wide) {
   const bool grid = c->sc.d_grid_cells && !(prm->flags & RT_FLAG_LAYER_BVH);
   const int place = grid ? c->sc.grid_placement : rtk::kGridGlobal;
-  return (wide ? rtk::kVarWide : 0) | ((prm->flags & RT_FLAG_OPEN_INTERVAL) ? rtk::kVarOpen : 0) |
+  // the extras' folded forms exist in the grid builds only (rt_kernel.hip launch_variant)
+  const int fold = grid && (prm->flags & RT_FLAG_ACCEL_BVH) ? c->sc.extras_fold : 0;
+  return (fold << rtk::kVarFoldShift) | (wide ? rtk::kVarWide : 0) | ((prm->flags & RT_FLAG_OPEN_INTERVAL) ? rtk::kVarOpen : 0) |
          ((prm->flags & RT_FLAG_METAL_UNIT_VECTOR) ? rtk::kVarMetalUnit : 0) |
          ((prm->flags & RT_FLAG_ACCEL_BVH) ? rtk::kVarBvh : 0) |
          ((prm->flags & RT_FLAG_COUNT_WORK) ? rtk::kVarStats : 0) | (grid ? rtk::kVarGrid : 0) |
@@ -953,6 +961,12 @@ int rt_internal_accel_info(const rt_scene_view *s, int grid_placement, double gr
   static const uint64_t kPlaceOut[3] = {RT_GRID_GLOBAL, RT_GRID_LDS, RT_GRID_CELLS_LDS};
   v[16] = cells ? kPlaceOut[a.grid_placement] : 0u;
   v[17] = (uint64_t)std::llround(g.scale * 1000.0);
+  v[18] = (uint64_t)a.extras_fold;
+  uint32_t cy_bits;
+  std::memcpy(&cy_bits, &a.extras_cy, sizeof cy_bits);
+  v[19] = cy_bits;
+  for (size_t k = 0; a.layer_mode && k < 16 && k < 2 * (size_t)a.n_extra_pairs; ++k)
+    v[20 + k] = (uint64_t)(a.slots[2 * (size_t)a.extra_pair0 + k] + 1);
   std::memcpy(out, v, std::min<size_t>(n_out, RT_ACCEL_INFO_N) * sizeof(uint64_t));
   return RT_OK;
 }

@@ -429,26 +429,62 @@ __device__ __forceinline__ void scan_pairs(const RT_CONST pair_geom *__restrict_
 // there: the ground, a candidate for almost every line) runs its own sequence
 // first (LEAD).  The candidate rule is order-independent, so the closest hit
 // is the same bits as a scan of the four in any order.
-template <bool OPEN, bool STATS, bool LEAD>
+//
+// FOLD (the first group only; the host's class of it, rt_layout.h kFold*, set
+// by bvh_builder's classify_extras from the centres' bit patterns) drops the
+// terms of the test that add an exact zero or are shared:
+//   kFoldLead: slot 0 has cx = cz = +0, so h = hy and g = gy (5 operations
+//              instead of 9);
+//   kFoldRest: slots 1-3 have one centre y, whose (hy, gy) pair is computed
+//              once (slot 1's; a padding slot's test is a miss with any cy: its
+//              ks is +inf), and cz = +0, so h = fma(cx, dx, hy) and g = fma(cx,
+//              ox2, gy) (5 each, plus the pair).
+// Why the result keeps its bits.  A dropped term is fma(+0, m, v) with m = dx,
+// dz, ox2 or oz2.  m is finite: d is normalised, and a wave with |O|^2 above
+// oref2 (inf included) scans instead; a NaN in o or d is already in nk1 and
+// o2, hence in v.  So the product is +-0, and v + (+-0) is v itself for every
+// v but a zero: there it is +0 unless both are -0, so the general form can
+// give +0 where the folded one keeps v = -0, and nothing else differs.  g is
+// read by e = fma(h, h, -g) alone: h h is +0 or above, and (+0) + (-+0) = +0
+// either way, so e, d = e - ks and c are the same bits.  h is read by e (as h
+// h: the same) and by candidate() as h - sq and h + sq with sq = sqrt_k(d) >=
+// 2^-48 > 0, where a zero of either sign gives -sq and +sq.  The roots, the
+// keys and the tie keys are therefore the general form's, bit for bit.
+template <bool OPEN, bool STATS, bool LEAD, int FOLD = 0>
 __device__ __forceinline__ void scan_extras(const RT_CONST pair_geom *__restrict__ g, int slot0,
                                             const RT_CONST int *__restrict__ orig, const ray_pre &r,
                                             float tmin, hit_state &hs, uint32_t &roots) {
+  static_assert(LEAD || !FOLD, "only the first group is classified");
   float h[4], d[4];
   uint32_t t[4];
   bool c[4];
+  float hy1 = 0.0f, gy1 = 0.0f;  // kFoldRest: the shared pair
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const pair_geom q = cload(g + j);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
+      const int k = 2 * j + s;
       const float cx = s ? q.cx.y : q.cx.x, cy = s ? q.cy.y : q.cy.x, cz = s ? q.cz.y : q.cz.x;
       const float ks = s ? q.ks.y : q.ks.x;
-      const float hy = fmaf(cy, r.dy.x, r.nk1.x);
-      const float gy = fmaf(cy, r.oy2.x, r.o2.x);
-      const float hh = fmaf(cz, r.dz.x, fmaf(cx, r.dx.x, hy));
-      const float gg = fmaf(cz, r.oz2.x, fmaf(cx, r.ox2.x, gy));
+      float hh, gg;
+      if (k == 0 && (FOLD & kFoldLead)) {
+        hh = fmaf(cy, r.dy.x, r.nk1.x);
+        gg = fmaf(cy, r.oy2.x, r.o2.x);
+      } else if (k > 0 && (FOLD & kFoldRest)) {
+        if (k == 1) {
+          hy1 = fmaf(cy, r.dy.x, r.nk1.x);
+          gy1 = fmaf(cy, r.oy2.x, r.o2.x);
+        }
+        hh = fmaf(cx, r.dx.x, hy1);
+        gg = fmaf(cx, r.ox2.x, gy1);
+      } else {
+        const float hy = fmaf(cy, r.dy.x, r.nk1.x);
+        const float gy = fmaf(cy, r.oy2.x, r.o2.x);
+        hh = fmaf(cz, r.dz.x, fmaf(cx, r.dx.x, hy));
+        gg = fmaf(cz, r.oz2.x, fmaf(cx, r.ox2.x, gy));
+      }
       const float ee = fmaf(hh, hh, -gg);
-      const int k = 2 * j + s;
       h[k] = hh;
       d[k] = ee - ks;
       c[k] = ee >= ks;
@@ -721,7 +757,8 @@ __device__ __forceinline__ void grid_walk(float ox, float oz, float ix, float iz
 // The scene parameters are re-read from the kernarg segment on entry
 // (kernargs()): they live in SGPRs for the walk only, not across the whole
 // bounce loop (SGPR pressure).
-template <bool OPEN, bool BVH, bool STATS, bool GRID, int GP>
+// FOLD: the grid build's form of the first extras group (scan_extras).
+template <bool OPEN, bool BVH, bool STATS, bool GRID, int GP, int FOLD>
 __device__ __forceinline__ hit_state closest_hit(float ox, float oy, float oz, float dx, float dy, float dz,
                                                  float tmin, work_ctr &wc) {
   const kparams p = kernargs();
@@ -781,7 +818,7 @@ __device__ __forceinline__ hit_state closest_hit(float ox, float oy, float oz, f
         // (kparams extra_geom / extra_orig: the host resolved the offsets)
         const RT_CONST pair_geom *__restrict__ xg = as_const(p.extra_geom);
         const RT_CONST int *__restrict__ xo = as_const(p.extra_orig);
-        if (p.n_extra_pairs > 0) scan_extras<OPEN, STATS, true>(xg, 0, xo, rp, tmin, hs, wc.roots);
+        if (p.n_extra_pairs > 0) scan_extras<OPEN, STATS, true, FOLD>(xg, 0, xo, rp, tmin, hs, wc.roots);
         for (int k = 2; k < p.n_extra_pairs; k += 2)
           scan_extras<OPEN, STATS, false>(xg + k, 2 * k, xo, rp, tmin, hs, wc.roots);
       } else {

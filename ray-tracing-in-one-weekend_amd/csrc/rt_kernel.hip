@@ -60,7 +60,9 @@ namespace rtk {
 // WIDE (scenes with an albedo above 1, rt_scene_upload): 64-bit pixel sums
 //  and the radiance clamps below; the default build's
 // code and registers are untouched.
-template <bool OPEN, bool METAL_UNIT, bool BVH, bool STATS, bool GRID, int GP, bool WIDE>
+// FOLD (grid builds; 0 elsewhere): the class of the scene's first extras group
+// (kFold*, chosen by the host), i.e. which terms of its test scan_extras drops.
+template <bool OPEN, bool METAL_UNIT, bool BVH, bool STATS, bool GRID, int GP, bool WIDE, int FOLD>
 __global__ __launch_bounds__(kBlock, 8) void render_kernel(const kparams p) {
   typedef typename std::conditional<WIDE, unsigned long long, uint32_t>::type sum_t;
   // Per-lane values that the bounce loop rarely needs are not kept live (VGPR
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(kBlock, 8) void render_kernel(const kparams p) {
   while (alive) {
     LP(kLpStep, tracing);
     hit_state hs = no_hit();
-    if (tracing) hs = closest_hit<OPEN, BVH, STATS, GRID, GP>(ox, oy, oz, dx, dy, dz, tmin, wc);
+    if (tracing) hs = closest_hit<OPEN, BVH, STATS, GRID, GP, FOLD>(ox, oy, oz, dx, dy, dz, tmin, wc);
     ++steps;
     const int best = best_of<OPEN>(hs);
     // lanes that end their path here (a miss) or hold a slot outside the frame
@@ -593,14 +595,17 @@ void launch_variant(unsigned blocks, size_t lds, hipStream_t st, const kparams &
   constexpr bool O = V & kVarOpen, U = V & kVarMetalUnit, B = V & kVarBvh, S = V & kVarStats;
   constexpr bool G = B && (V & kVarGrid), W = V & kVarWide;
   constexpr int P = G ? ((V >> kVarPlaceShift) & 3) % 3 : kGridGlobal;
-  render_kernel<O, U, B, S, G, P, W><<<blocks, kBlock, G ? lds : 0, st>>>(kp);
+  // the first extras group's class: a build of its own for the grid walk
+  // only (the scan and BVH builds are one kernel each whatever the bits say)
+  constexpr int F = G ? (V >> kVarFoldShift) & 3 : 0;
+  render_kernel<O, U, B, S, G, P, W, F><<<blocks, kBlock, G ? lds : 0, st>>>(kp);
 }
 using launch_fn = void (*)(unsigned, size_t, hipStream_t, const kparams &);
 template <int... V>
 constexpr auto launch_table(std::integer_sequence<int, V...>) {
   return std::array<launch_fn, sizeof...(V)>{&launch_variant<V>...};
 }
-constexpr auto kLaunch = launch_table(std::make_integer_sequence<int, 2 * kVarWide>{});
+constexpr auto kLaunch = launch_table(std::make_integer_sequence<int, kVarCount>{});
 
 hipError_t launch_render(int variant, unsigned blocks, size_t lds_bytes, hipStream_t st, const kparams &kp) {
   if (variant < 0 || variant >= (int)kLaunch.size()) return hipErrorInvalidValue;

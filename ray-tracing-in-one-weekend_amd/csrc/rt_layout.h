@@ -107,6 +107,13 @@ struct __attribute__((aligned(16))) shade_rec {
 //                at a coarser cell size).
 enum { kGridGlobal = 0, kGridLds = 1, kGridCells = 2 };
 
+// The first extras group of a layer scene, classified by its centres' bit
+// patterns (bvh_builder::classify_extras; the grid build's scan_extras drops
+// the terms a class makes exact zeros or shares):
+//   kFoldLead: slot 0 (the largest extra: the ground) has cx = cz = +0;
+//   kFoldRest: the group's other spheres (1 to 3) have one centre y and cz = +0.
+enum { kFoldLead = RT_EXTRAS_AXIAL, kFoldRest = RT_EXTRAS_COAXIAL };
+
 struct kparams {
   rt_camera cam;
   int width, height, spp, max_depth;
@@ -173,6 +180,11 @@ struct kparams {
   // kernel does no 64-bit index arithmetic per step
   const struct pair_geom *extra_geom;
   const int *extra_orig;
+  // the first extras group's class (kFold* bits, bvh_builder::classify_extras)
+  // and the centre y its coaxial spheres share; the host picks the grid
+  // build's scan_extras form from the class (kVarFoldShift)
+  int extras_fold;
+  float extras_cy;
 };
 
 // LDS bytes of the grid copy of one block
@@ -198,7 +210,9 @@ enum {
   kVarStats = 8,      // RT_FLAG_COUNT_WORK (and the pilot)
   kVarGrid = 16,      // the layer-grid walk (with kVarBvh on a layer scene)
   kVarPlaceShift = 5, // bits 5-6: the grid placement (kGridGlobal / kGridLds / kGridCells)
-  kVarWide = 128      // 64-bit pixel sums (a scene albedo above 1)
+  kVarWide = 128,     // 64-bit pixel sums (a scene albedo above 1)
+  kVarFoldShift = 8,  // bits 8-9: the first extras group's class (kFold*; the grid walk only)
+  kVarCount = 1024
 };
 hipError_t launch_render(int variant, unsigned blocks, size_t lds_bytes, hipStream_t st, const kparams &kp);
 hipError_t launch_finish_sums(uint32_t *frame, uint64_t n, float qinv, hipStream_t st);

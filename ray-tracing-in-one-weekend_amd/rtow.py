@@ -621,6 +621,24 @@ def sealed(scene):
     return out[:scene.n].astype(bool)
 
 
+RT_EXTRAS_AXIAL, RT_EXTRAS_COAXIAL = 1, 2
+
+
+def extras_info(scene):
+    """The extras of a layer scene (the spheres off the layer) as
+    rt_scene_upload would lay them out, computed on the host
+    (rt_internal_accel_info's values 18..35; no device): (class bits
+    RT_EXTRAS_* of the first group of four, the centre y its coaxial spheres
+    share as a float32, the original index of each extras slot in scan order,
+    -1 = padding; at most the first 16 slots)."""
+    v = scene.view()
+    out = np.zeros(36, np.uint64)
+    check(lib().rt_internal_accel_info(ctypes.byref(v), 0, 0.0, out.ctypes.data, out.size), "rt_internal_accel_info")
+    n = min(2 * int(out[4]), 16) if out[2] else 0
+    cy = np.array([int(out[19])], np.uint32).view(np.float32)[0]
+    return int(out[18]), cy, out[20:20 + n].astype(np.int64).astype(np.int32) - 1
+
+
 LAUNCH_PLAN_KEYS = ("ranges", "chunks", "units", "entries", "launches")
 
 

@@ -19,7 +19,7 @@ out = sys.argv[1]
 f = glob.glob(out + "/**/*counter_collection.csv", recursive=True)[0]
 acc = collections.defaultdict(float)
 for row in csv.DictReader(open(f)):
-    if os.environ.get("KERNEL", "render_kernel<false, false, true, false, true, 1, false>") in row["Kernel_Name"]:
+    if os.environ.get("KERNEL", "render_kernel<false, false, true, false, true, 1, false, 3>") in row["Kernel_Name"]:
         acc[row["Counter_Name"]] += float(row["Counter_Value"])
 print(out.split("/")[-1], {k: f"{v:.4g}" for k, v in sorted(acc.items())})
 PY
