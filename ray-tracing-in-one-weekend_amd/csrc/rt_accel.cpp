@@ -28,7 +28,10 @@ namespace {
 // origins |O| <= oref (the kernel scans everything for a wave-step that has
 // any lane beyond oref), and node boxes get a further relative 2^-18 plus an
 // outward fp32 rounding to cover the slab test's own rounding.
-struct bvh_builder {
+//
+// The builder is the scene's scene_dims (run() fills every field) plus the
+// arrays and the grid they count.
+struct bvh_builder : scene_dims {
   struct box {
     double lo[3], hi[3];
   };
@@ -95,10 +98,10 @@ struct bvh_builder {
     box all = empty();
     for (uint32_t i = b; i < e; ++i) grow(all, sb[ord[i]]);
     tree[id].b = all;
-    const uint32_t n = e - b;
-    if (n <= (uint32_t)max_leaf) {
+    const uint32_t cnt = e - b;
+    if (cnt <= (uint32_t)max_leaf) {
       const uint32_t first_slot = (uint32_t)slots.size();
-      const uint32_t width = n <= 2 ? 2u : (uint32_t)kLeaf;  // one pair or two
+      const uint32_t width = cnt <= 2 ? 2u : (uint32_t)kLeaf;  // one pair or two
       for (uint32_t i = b; i < e; ++i) slots.push_back((int)ord[i]);
       while (slots.size() < first_slot + width) slots.push_back(-1);
       tree[id].leaf = (first_slot / 2 + 1) | (width == 4 ? kTwoPairs : 0u);
@@ -107,26 +110,26 @@ struct bvh_builder {
     // SAH over the 3 axes, sweeping sorted centroids (ties: original index)
     double best_cost = 1e300;
     int best_axis = 0;
-    uint32_t best_split = b + n / 2;
-    std::vector<double> left(n);
+    uint32_t best_split = b + cnt / 2;
+    std::vector<double> left(cnt);
     for (int ax = 0; ax < 3; ++ax) {
       std::sort(ord.begin() + b, ord.begin() + e, [&](uint32_t x, uint32_t y) {
         const double cx = cen[3 * x + ax], cy = cen[3 * y + ax];
         return cx < cy || (cx == cy && x < y);
       });
       box acc = empty();
-      for (uint32_t i = 0; i < n; ++i) {
+      for (uint32_t i = 0; i < cnt; ++i) {
         grow(acc, sb[ord[b + i]]);
         left[i] = area(acc);
       }
       acc = empty();
-      for (uint32_t i = n - 1; i >= 1; --i) {
+      for (uint32_t i = cnt - 1; i >= 1; --i) {
         grow(acc, sb[ord[b + i]]);
-        // split before i: left = [0, i), right = [i, n).  Spheres are tested
+        // split before i: left = [0, i), right = [i, cnt).  Spheres are tested
         // in pairs (one v_pk_fma_f32 chain per pair), so a subtree costs its
         // area times its pair count, ceil(count / 2): 3 spheres cost as much
         // as 4, and splits into even counts are preferred (397 vs 412 ms)
-        const double cost = left[i - 1] * ((i + 1) / 2) + area(acc) * ((n - i + 1) / 2);
+        const double cost = left[i - 1] * ((i + 1) / 2) + area(acc) * ((cnt - i + 1) / 2);
         if (cost < best_cost) {
           best_cost = cost;
           best_axis = ax;
@@ -212,7 +215,6 @@ struct bvh_builder {
     nd.by[1] = h[1];
     nd.bz[0] = nd.bz[1] = 0.0f;
   }
-  size_t per_order = 0;
   // oref: the ray-origin bound the padding is valid for -- 64 or 16 beyond the
   // farthest sphere of radius <= 10, whichever is larger (the huge ground
   // sphere does not count: rays only start on its visible cap)
@@ -227,10 +229,10 @@ struct bvh_builder {
     }
     return std::max(64.0, far + 16.0);
   }
-  double oref = 64.0;
   uint32_t n_layer = 0;  // layer mode: spheres in the layer (ord[0, n_layer))
   void run(const rt_scene_view *s) {
-    const uint32_t n = s->n;
+    n = s->n;
+    n_pad = (n + kSpherePad - 1) / kSpherePad * kSpherePad;
     oref = origin_bound(s);
     sb.resize(n);
     cen.resize(3 * (size_t)n);
@@ -264,9 +266,12 @@ struct bvh_builder {
       // time (one s_load_dwordx16, two independent chains)
       while ((slots.size() - 2 * extra_pair0) % 4) slots.push_back(-1);
       n_extra_pairs = (uint32_t)slots.size() / 2 - extra_pair0;
+      if (n_extra_pairs)
+        extras_fold = classify_extras(s, slots.data() + 2 * (size_t)extra_pair0, 2 * (size_t)n_extra_pairs, &extras_cy);
       n_layer = n_tree;
       build_grid(s, n_tree);
     }
+    n_slots = slots.size();
   }
   // Layer grid: square x-z cells of side g over the layer spheres' padded
   // boxes; a cell lists every layer sphere whose padded box comes within pad
@@ -376,11 +381,7 @@ struct bvh_builder {
   // rest are scanned as plain pairs.  Reorders ord:
   // layer spheres first; returns their count (n when not in layer mode).
   static constexpr uint32_t kMinLayer = 64, kMaxExtra = 16;
-  bool layer_mode = false;
-  float layer_lo = 0.0f, layer_hi = 0.0f, layer_cy = 0.0f;
-  uint32_t extra_pair0 = 0, n_extra_pairs = 0;
   uint32_t split_layer(const rt_scene_view *s) {
-    const uint32_t n = s->n;
     std::vector<std::pair<float, float>> key(n);
     for (uint32_t i = 0; i < n; ++i) key[i] = {s->cy[i], std::fabs(s->radius[i])};
     std::vector<uint32_t> by_key(n);
@@ -544,8 +545,10 @@ void build_accel(const rt_scene_view *s, const accel_options &o, accel_build &a,
   if (fitter) *fitter = nullptr;
   const uint32_t n = s->n;
   a = accel_build{};
-  a.n = n;
-  a.n_pad = (n + kSpherePad - 1) / kSpherePad * kSpherePad;
+  bvh_builder bb;
+  bb.configure(o, o.grid_scale);
+  bb.run(s);
+  static_cast<scene_dims &>(a) = bb;
   a.scan_geom.assign(a.n_pad / 2, pair_geom{});
   for (uint32_t i = 0; i < a.n_pad; ++i) fill_slot(a.scan_geom[i / 2], i & 1, s, i < n ? (int)i : -1);
   a.shade.assign(n, shade_rec{});
@@ -575,9 +578,6 @@ void build_accel(const rt_scene_view *s, const accel_options &o, accel_build &a,
     r.r0 = (float)(r0 * r0);
     r.sealed = sealed[i];
   }
-  bvh_builder bb;
-  bb.configure(o, o.grid_scale);
-  bb.run(s);
   // Grid placement.  The whole grid in LDS when it fits the
   // per-block budget (u16 LDS addresses: < 4096 items); else, for auto or
   // kGridCells, only the u16 cell starts in LDS -- the cells rebuilt coarser
@@ -614,17 +614,6 @@ void build_accel(const rt_scene_view *s, const accel_options &o, accel_build &a,
   for (size_t k = 0; k < bb.slots.size(); ++k) fill_slot(a.bvh_geom[k / 2], (int)(k & 1), s, bb.slots[k]);
   a.slots = bb.slots;
   a.nodes = bb.nodes;
-  a.per_order = bb.per_order;
-  a.oref = bb.oref;
-  a.layer_mode = bb.layer_mode;
-  a.layer_lo = bb.layer_lo;
-  a.layer_hi = bb.layer_hi;
-  a.layer_cy = bb.layer_cy;
-  a.extra_pair0 = bb.extra_pair0;
-  a.n_extra_pairs = bb.n_extra_pairs;
-  if (a.layer_mode && a.n_extra_pairs)
-    a.extras_fold = classify_extras(s, a.slots.data() + 2 * (size_t)a.extra_pair0, 2 * (size_t)a.n_extra_pairs,
-                                    &a.extras_cy);
   a.grid = bb.grid;
   a.grid_placement = bb.grid.cells.empty() ? kGridGlobal : place;
   // the builder's layer split and boxes go on into the grid fitter

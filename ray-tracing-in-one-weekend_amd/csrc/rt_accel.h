@@ -47,21 +47,33 @@ struct grid_geom : grid_dims {
   }
 };
 
-// everything rt_scene_upload copies to the device, plus the builder's facts
-struct accel_build {
-  uint32_t n = 0, n_pad = 0;
-  std::vector<pair_geom> scan_geom;  // brute-force order, n_pad / 2 pairs
-  std::vector<shade_rec> shade;      // n
-  std::vector<pair_geom> bvh_geom;   // BVH leaf order (+ extras in layer mode)
-  std::vector<int> slots;            // BVH slot -> original index, -1 padding
-  std::vector<bvh_node> nodes;       // 8 DFS orders
-  size_t per_order = 0;
-  double oref = 64.0;
+// The scalar facts of a built scene, each once, in one spelling from the builder
+// to the context (scene_kparams in rt_api.cpp turns them into the kernel's).
+struct scene_dims {
+  uint32_t n = 0, n_pad = 0;  // spheres; scan slots (whole kSpherePad groups)
+  size_t per_order = 0;       // BVH nodes per DFS order (the node array holds 8 orders)
+  size_t n_slots = 0;         // BVH slots (leaves, then the extras in layer mode)
+  double oref = 64.0;         // the ray-origin bound the boxes' padding is valid for
   bool layer_mode = false;
   float layer_lo = 0.0f, layer_hi = 0.0f, layer_cy = 0.0f;
   uint32_t extra_pair0 = 0, n_extra_pairs = 0;
   int extras_fold = 0;     // kFold* bits of the first extras group (classify_extras)
   float extras_cy = 0.0f;  // kFoldRest: the centre y its spheres share
+  bool operator==(const scene_dims &o) const {
+    return n == o.n && n_pad == o.n_pad && per_order == o.per_order && n_slots == o.n_slots && oref == o.oref &&
+           layer_mode == o.layer_mode && layer_lo == o.layer_lo && layer_hi == o.layer_hi &&
+           layer_cy == o.layer_cy && extra_pair0 == o.extra_pair0 && n_extra_pairs == o.n_extra_pairs &&
+           extras_fold == o.extras_fold && extras_cy == o.extras_cy;
+  }
+};
+
+// everything rt_scene_upload copies to the device, plus the builder's facts
+struct accel_build : scene_dims {
+  std::vector<pair_geom> scan_geom;  // brute-force order, n_pad / 2 pairs
+  std::vector<shade_rec> shade;      // n
+  std::vector<pair_geom> bvh_geom;   // BVH leaf order (+ extras in layer mode)
+  std::vector<int> slots;            // BVH slot -> original index, -1 padding (n_slots)
+  std::vector<bvh_node> nodes;       // 8 DFS orders of per_order
   grid_geom grid;                        // layer grid (cells empty: none)
   int grid_placement = kGridGlobal;
 };

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 #include <utility>
 #include <vector>
@@ -28,24 +29,17 @@ extern "C" hipError_t rt_internal_block_order(const uint32_t *tile_cost, uint32_
                                               uint32_t *order, hipStream_t st);
 
 // ------------------------------------------------------------ context ----
-// Everything that belongs to the uploaded scene: rt_scene_upload fills one and
-// moves it into the context, free_scene frees what it owns and starts afresh.
+// Everything that belongs to the uploaded scene, freed with the record:
+// rt_scene_upload fills one and moves it into the context.
 struct scene_state {
-  rtk::pair_geom *d_geom = nullptr;      // brute-force order
-  rtk::pair_geom *d_bvh_geom = nullptr;  // BVH leaf order
-  rtk::bvh_node *d_nodes = nullptr;
-  int *d_orig = nullptr;                 // BVH slot -> original index (-1 = padding)
-  rtk::shade_rec *d_shade = nullptr;
-  uint32_t n_spheres = 0, n_pad = 0, n_nodes = 0, n_bvh_slots = 0;
-  float oref2 = 0.0f;
-  bool layer_mode = false;
-  float layer_lo = 0.0f, layer_hi = 0.0f, layer_cy = 0.0f;
-  uint32_t extra_pair0 = 0, n_extra_pairs = 0;
-  int extras_fold = 0;     // rtk::kFold* bits of the first extras group
-  float extras_cy = 0.0f;  // kFoldRest: the centre y its spheres share
-  uint32_t *d_grid_cells = nullptr;  // layer grid (nullptr: none)
-  float *d_grid_items = nullptr;
-  size_t cells_cap = 0, items_cap = 0;  // d_grid_cells / d_grid_items capacity (u32 / items)
+  rtk::scene_dims dims;                      // the builder's facts (scene_kparams)
+  rt_device_buf<rtk::pair_geom> d_geom;      // brute-force order
+  rt_device_buf<rtk::pair_geom> d_bvh_geom;  // BVH leaf order
+  rt_device_buf<rtk::bvh_node> d_nodes;
+  rt_device_buf<int> d_orig;                 // BVH slot -> original index (-1 = padding)
+  rt_device_buf<rtk::shade_rec> d_shade;
+  rt_device_buf<uint32_t> d_grid_cells;  // layer grid (p nullptr: none)
+  rt_device_buf<float> d_grid_items;     // 4 floats per item
   size_t grid_n_items = 0;
   int grid_placement = rtk::kGridGlobal;  // rtk::kGrid*: where a launch keeps the grid
   rtk::grid_dims grid;                    // of the grid in the buffers (scale NaN: of neither, after a failed copy)
@@ -55,7 +49,7 @@ struct scene_state {
   // the layer grid's cell size fitted per frame geometry (rtk::grid_fitter,
   // DESIGN.md 3.3): the fitter, the geometry its grid was fitted for, and the
   // host copy the last refit uploads from (the context's ev_fit: after that copy)
-  rtk::grid_fitter *fitter = nullptr;
+  std::unique_ptr<rtk::grid_fitter> fitter;
   std::vector<uint64_t> fit_key;
   rtk::grid_geom fit_grid;
   bool fit_pending = false;
@@ -69,10 +63,9 @@ struct rt_context {
   hipEvent_t ev_fit = nullptr;
   bool grid_fit = true;         // RT_OPT_GRID_FIT
   bool grid_scale_set = false;  // RT_OPT_GRID_SCALE given: no fitting
-  unsigned long long *d_counters = nullptr;
-  float *d_frame = nullptr;
-  size_t frame_floats = 0;
-  // block schedule from a pilot render, cached per frame geometry
+  rt_device_buf<unsigned long long> d_counters;
+  rt_device_buf<float> d_frame;  // rt_render's frame (only it uses it, and it returns after its work is done)
+  // block schedule from a pilot render, cached per frame geometry (stream-ordered allocation)
   uint32_t *d_order = nullptr;
   size_t order_n = 0;
   std::vector<uint64_t> order_key;
@@ -93,10 +86,9 @@ struct rt_context {
   std::vector<hipEvent_t> ev_launch;
   double tonemap_thr64[257];  // rt_tonemap_async level thresholds (see tonemap_thresholds)
   float tonemap_thr32[257];
-  double *d_thr64 = nullptr;
-  float *d_thr32 = nullptr;
-  uint64_t *d_wide = nullptr;  // 64-bit scratch frame (sc.max_albedo above 1, atomic renders)
-  size_t wide_n = 0;
+  rt_device_buf<double> d_thr64;
+  rt_device_buf<float> d_thr32;
+  rt_device_buf<uint64_t> d_wide;  // 64-bit scratch frame (sc.max_albedo above 1, atomic renders)
   // rt_context_set_option
   rtk::accel_options opt;
   double launch_samples = rtk::kLaunchSamples;
@@ -135,31 +127,18 @@ bool params_ok(const rt_params *p) {
          (uint64_t)p->width * (uint64_t)p->height < (1ull << 32);
 }
 
-// frees what the record owns; it is then a fresh one
-void release(scene_state &s) {
-  for (void *d : {(void *)s.d_geom, (void *)s.d_bvh_geom, (void *)s.d_nodes, (void *)s.d_orig, (void *)s.d_shade,
-                  (void *)s.d_grid_cells, (void *)s.d_grid_items})
-    (void)hipFree(d);
-  delete s.fitter;
-  s = scene_state{};
-}
-
-void free_scene(rt_context *c) {
-  release(c->sc);
-  c->order_key.clear();  // the pilot's tile costs belong to the old scene
-}
-
 // key += the camera's words
 void append_camera(std::vector<uint64_t> &key, const rt_camera *cam) {
   const uint32_t *cw = reinterpret_cast<const uint32_t *>(cam);
   for (size_t k = 0; k < sizeof(rt_camera) / 4; ++k) key.push_back(cw[k]);
 }
 
+// (an empty vector still gets a buffer: a scene of no spheres is a scene)
 template <class T>
-hipError_t upload_vec(T **dst, const std::vector<T> &v, hipStream_t st) {
-  hipError_t e = hipMalloc(dst, sizeof(T) * (v.empty() ? 1 : v.size()));
+hipError_t upload_vec(rt_device_buf<T> &dst, const std::vector<T> &v, hipStream_t st) {
+  hipError_t e = dst.grow(v.empty() ? 1 : v.size());
   if (e == hipSuccess && !v.empty())
-    e = hipMemcpyAsync(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(dst.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st);
   return e;
 }
 
@@ -198,6 +177,16 @@ sum_fmt sum_format(int spp, int max_depth, double max_albedo) {
   const int ceil_log2 = m == 0.5 ? e - 1 : e;
   return {true, sum_bits(spp) + 31 - ceil_log2, vc};
 }
+// the format's kernel arguments
+void sum_kparams(const sum_fmt &fmt, rtk::kparams &kp) {
+  kp.qscale = std::ldexp(1.0f, fmt.f);
+  kp.qinv = std::ldexp(1.0f, -fmt.f);
+  kp.vcap = fmt.vcap;
+  // F < 20 (spp >= 4096): truncation would bias a dark pixel by up to 2^-F per
+  // sample (0.03 level at F = 20); stochastic rounding is unbiased for every
+  // spp (DESIGN.md 2, step 6)
+  kp.dither = fmt.f < 20 ? 1 : 0;
+}
 
 }  // namespace
 
@@ -233,12 +222,12 @@ int rt_context_create(int device_ordinal, rt_context **out) {
     if ((e = hipEventCreate(&c->ev0)) != hipSuccess) break;
     if ((e = hipEventCreate(&c->ev1)) != hipSuccess) break;
     if ((e = hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming)) != hipSuccess) break;
-    if ((e = hipMalloc(&c->d_counters, 8 * rtk::kCounterSlots * sizeof(unsigned long long))) != hipSuccess) break;
+    if ((e = c->d_counters.grow(8 * rtk::kCounterSlots)) != hipSuccess) break;
     tonemap_thresholds(c->tonemap_thr64, c->tonemap_thr32);
-    if ((e = hipMalloc(&c->d_thr64, sizeof c->tonemap_thr64)) != hipSuccess) break;
-    if ((e = hipMalloc(&c->d_thr32, sizeof c->tonemap_thr32)) != hipSuccess) break;
-    if ((e = hipMemcpy(c->d_thr64, c->tonemap_thr64, sizeof c->tonemap_thr64, hipMemcpyHostToDevice)) != hipSuccess) break;
-    if ((e = hipMemcpy(c->d_thr32, c->tonemap_thr32, sizeof c->tonemap_thr32, hipMemcpyHostToDevice)) != hipSuccess) break;
+    if ((e = c->d_thr64.grow(257)) != hipSuccess) break;
+    if ((e = c->d_thr32.grow(257)) != hipSuccess) break;
+    if ((e = hipMemcpy(c->d_thr64.p, c->tonemap_thr64, sizeof c->tonemap_thr64, hipMemcpyHostToDevice)) != hipSuccess) break;
+    if ((e = hipMemcpy(c->d_thr32.p, c->tonemap_thr32, sizeof c->tonemap_thr32, hipMemcpyHostToDevice)) != hipSuccess) break;
     if ((e = rtk::upload_turn_table()) != hipSuccess) break;
   } while (0);
   if (e != hipSuccess) {
@@ -256,20 +245,14 @@ void rt_context_destroy(rt_context *c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();  // renders on caller streams may still use the buffers
   }
-  free_scene(c);
-  (void)hipFree(c->d_counters);
-  (void)hipFree(c->d_frame);
   (void)hipFree(c->d_order);
-  (void)hipFree(c->d_wide);
-  (void)hipFree(c->d_thr64);
-  (void)hipFree(c->d_thr32);
   for (hipEvent_t ev : c->ev_launch) (void)hipEventDestroy(ev);
   if (c->ev_done) (void)hipEventDestroy(c->ev_done);
   if (c->ev_fit) (void)hipEventDestroy(c->ev_fit);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // (frees the buffers the context and its scene own)
 }
 
 int rt_context_set_option(rt_context *c, int option, double v) {
@@ -321,21 +304,11 @@ int rt_scene_upload(rt_context *c, const rt_scene_view *s) {
   rtk::accel_options o = c->opt;
   o.wide = rtk::max_albedo(s) > 1.0;
   scene_state sc;  // becomes the context's once its copies have completed
-  rtk::build_accel(s, o, a, c->grid_fit && !c->grid_scale_set ? &sc.fitter : nullptr);
-  sc.n_spheres = a.n;
+  rtk::grid_fitter *fitter = nullptr;
+  rtk::build_accel(s, o, a, c->grid_fit && !c->grid_scale_set ? &fitter : nullptr);
+  sc.fitter.reset(fitter);
+  sc.dims = a;
   sc.max_albedo = rtk::max_albedo(s);
-  sc.n_pad = a.n_pad;
-  sc.n_nodes = (uint32_t)a.per_order;  // nodes holds 8 orders of this many
-  sc.n_bvh_slots = (uint32_t)a.slots.size();
-  sc.oref2 = (float)(0.99 * a.oref * a.oref);
-  sc.layer_mode = a.layer_mode;
-  sc.layer_lo = a.layer_lo;
-  sc.layer_cy = a.layer_cy;
-  sc.layer_hi = a.layer_hi;
-  sc.extra_pair0 = a.extra_pair0;
-  sc.n_extra_pairs = a.n_extra_pairs;
-  sc.extras_fold = a.extras_fold;
-  sc.extras_cy = a.extras_cy;
   sc.grid = a.grid;
 
   // renders enqueued on caller streams may still read the old scene: they
@@ -344,28 +317,22 @@ int rt_scene_upload(rt_context *c, const rt_scene_view *s) {
   hipError_t e = hipSetDevice(c->device);
   if (e == hipSuccess && c->have_done) e = hipEventSynchronize(c->ev_done);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {  // (the old scene stays)
-    release(sc);
-    return hip_fail(e);
-  }
-  free_scene(c);
-  e = upload_vec(&sc.d_geom, a.scan_geom, c->stream);
-  if (e == hipSuccess) e = upload_vec(&sc.d_bvh_geom, a.bvh_geom, c->stream);
-  if (e == hipSuccess) e = upload_vec(&sc.d_nodes, a.nodes, c->stream);
-  if (e == hipSuccess) e = upload_vec(&sc.d_orig, a.slots, c->stream);
-  if (e == hipSuccess) e = upload_vec(&sc.d_shade, a.shade, c->stream);
+  if (e != hipSuccess) return hip_fail(e);  // (the old scene stays)
+  c->sc = scene_state{};                    // frees the old scene before the new one is allocated
+  c->order_key.clear();                     // the pilot's tile costs belong to the old scene
+  e = upload_vec(sc.d_geom, a.scan_geom, c->stream);
+  if (e == hipSuccess) e = upload_vec(sc.d_bvh_geom, a.bvh_geom, c->stream);
+  if (e == hipSuccess) e = upload_vec(sc.d_nodes, a.nodes, c->stream);
+  if (e == hipSuccess) e = upload_vec(sc.d_orig, a.slots, c->stream);
+  if (e == hipSuccess) e = upload_vec(sc.d_shade, a.shade, c->stream);
   if (e == hipSuccess && !a.grid.cells.empty()) {
-    e = upload_vec(&sc.d_grid_cells, a.grid.cells, c->stream);
-    if (e == hipSuccess) e = upload_vec(&sc.d_grid_items, a.grid.items, c->stream);
-    sc.cells_cap = a.grid.cells.size();
-    sc.items_cap = sc.grid_n_items = a.grid.items.size() / 4;
+    e = upload_vec(sc.d_grid_cells, a.grid.cells, c->stream);
+    if (e == hipSuccess) e = upload_vec(sc.d_grid_items, a.grid.items, c->stream);
+    sc.grid_n_items = a.grid.items.size() / 4;
     sc.grid_placement = a.grid_placement;
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {  // (no scene)
-    release(sc);
-    return hip_fail(e);
-  }
+  if (e != hipSuccess) return hip_fail(e);  // (no scene)
   c->sc = std::move(sc);
   return RT_OK;
 }
@@ -387,13 +354,13 @@ uint64_t valid_rows(const rt_params *prm) {
   return n;
 }
 
-// the kernel arguments of a layer grid in device memory (the one place that
-// knows both spellings of its geometry, rtk::grid_dims' and rtk::kparams')
-void grid_kparams(const rtk::grid_dims &g, const uint32_t *d_cells, const float *d_items, size_t n_items,
-                  rtk::kparams &kp) {
-  kp.grid_cells = d_cells;
-  kp.grid_items = (const rtk::f4 *)d_items;
-  kp.grid_n_items = (int)n_items;
+// the kernel arguments of the scene's layer grid in device memory (the one place
+// that knows both spellings of its geometry, rtk::grid_dims' and rtk::kparams')
+void grid_kparams(const scene_state &s, rtk::kparams &kp) {
+  const rtk::grid_dims &g = s.grid;
+  kp.grid_cells = s.d_grid_cells.p;
+  kp.grid_items = (const rtk::f4 *)s.d_grid_items.p;
+  kp.grid_n_items = (int)s.grid_n_items;
   kp.grid_n_cells = g.nx * g.nz;
   kp.grid_x0 = g.x0;
   kp.grid_xi = g.xi;
@@ -405,6 +372,29 @@ void grid_kparams(const rtk::grid_dims &g, const uint32_t *d_cells, const float 
   kp.grid_invg = g.g > 0.0f ? 1.0f / g.g : 0.0f;
   kp.grid_nx = g.nx;
   kp.grid_nz = g.nz;
+}
+
+// the kernel arguments of a built scene in device memory (the one place that
+// knows both spellings of its facts, rtk::scene_dims' and rtk::kparams')
+void scene_kparams(const scene_state &s, rtk::kparams &kp) {
+  const rtk::scene_dims &d = s.dims;
+  kp.n_pad = (int)d.n_pad;
+  kp.n_nodes = (int)(uint32_t)d.per_order;  // nodes holds 8 orders of this many
+  kp.oref2 = (float)(0.99 * d.oref * d.oref);
+  kp.layer = rtk::f2{d.layer_lo, d.layer_hi};
+  kp.layer_mode = d.layer_mode ? 1 : 0;
+  kp.layer_cy = d.layer_cy;
+  kp.extra_pair0 = (int)d.extra_pair0;
+  kp.n_extra_pairs = (int)d.n_extra_pairs;
+  kp.extras_fold = d.extras_fold;
+  kp.extras_cy = d.extras_cy;
+  kp.scan_geom = s.d_geom.p;
+  kp.geom = s.d_bvh_geom.p;
+  kp.nodes = s.d_nodes.p;
+  kp.orig = s.d_orig.p;
+  kp.extra_geom = s.d_bvh_geom.p ? s.d_bvh_geom.p + d.extra_pair0 : nullptr;
+  kp.extra_orig = s.d_orig.p ? s.d_orig.p + 2 * (size_t)d.extra_pair0 : nullptr;
+  kp.shade = s.d_shade.p;
 }
 
 // The kernel arguments of a render of (cam, prm) into accum_rgb with the
@@ -424,31 +414,14 @@ void fill_kparams(const rt_context *c, const rt_camera *cam, const rt_params *pr
   kp.band_offset = prm->band_offset;
   kp.local_rows = prm->local_rows;
   kp.tiles_x = (prm->width + rtk::kTile - 1) / rtk::kTile;
-  const scene_state &s = c->sc;
-  kp.n_pad = (int)s.n_pad;
-  kp.n_nodes = (int)s.n_nodes;
-  kp.oref2 = s.oref2;
-  kp.layer = rtk::f2{s.layer_lo, s.layer_hi};
-  kp.layer_mode = s.layer_mode ? 1 : 0;
-  kp.layer_cy = s.layer_cy;
-  kp.extra_pair0 = (int)s.extra_pair0;
-  kp.n_extra_pairs = (int)s.n_extra_pairs;
-  kp.extras_fold = s.extras_fold;
-  kp.extras_cy = s.extras_cy;
-  grid_kparams(s.grid, s.d_grid_cells, s.d_grid_items, s.grid_n_items, kp);
+  scene_kparams(c->sc, kp);
+  grid_kparams(c->sc, kp);
   kp.seed32 = (uint32_t)prm->seed ^ ((uint32_t)(prm->seed >> 32) * 0x9E3779B9u);
   kp.flags = prm->flags;
   kp.inv_wm1 = (float)(1.0 / (prm->width - 1));
   kp.inv_hm1 = (float)(1.0 / (prm->height - 1));
-  kp.scan_geom = s.d_geom;
-  kp.geom = s.d_bvh_geom;
-  kp.nodes = s.d_nodes;
-  kp.orig = s.d_orig;
-  kp.extra_geom = s.d_bvh_geom ? s.d_bvh_geom + s.extra_pair0 : nullptr;
-  kp.extra_orig = s.d_orig ? s.d_orig + 2 * (size_t)s.extra_pair0 : nullptr;
-  kp.shade = s.d_shade;
   kp.out = accum_rgb;
-  kp.counters = c->d_counters;
+  kp.counters = c->d_counters.p;
   {
     uint32_t w = (uint32_t)prm->width, sh = 0;
     while (!(w & 1u)) {
@@ -462,17 +435,16 @@ void fill_kparams(const rt_context *c, const rt_camera *cam, const rt_params *pr
   }
 }
 
-// render_kernel variant bits of a render (rt_layout.h kVar*)
-int render_variant(const rt_context *c, const rt_params *prm, bool wide) {
-  const bool grid = c->sc.d_grid_cells && !(prm->flags & RT_FLAG_LAYER_BVH);
-  const int place = grid ? c->sc.grid_placement : rtk::kGridGlobal;
+// render_kernel variant bits of a render (rt_layout.h kVar*); whether it walks
+// the layer grid, and where that lives, are frame_begin's decisions
+int render_variant(const rt_frame_setup &fs, const rt_params *prm, bool wide) {
   // the extras' folded forms exist in the grid builds only (rt_kernel.hip launch_variant)
-  const int fold = grid && (prm->flags & RT_FLAG_ACCEL_BVH) ? c->sc.extras_fold : 0;
+  const int fold = fs.grid && (prm->flags & RT_FLAG_ACCEL_BVH) ? fs.kp.extras_fold : 0;
   return (fold << rtk::kVarFoldShift) | (wide ? rtk::kVarWide : 0) | ((prm->flags & RT_FLAG_OPEN_INTERVAL) ? rtk::kVarOpen : 0) |
          ((prm->flags & RT_FLAG_METAL_UNIT_VECTOR) ? rtk::kVarMetalUnit : 0) |
          ((prm->flags & RT_FLAG_ACCEL_BVH) ? rtk::kVarBvh : 0) |
-         ((prm->flags & RT_FLAG_COUNT_WORK) ? rtk::kVarStats : 0) | (grid ? rtk::kVarGrid : 0) |
-         (place << rtk::kVarPlaceShift);
+         ((prm->flags & RT_FLAG_COUNT_WORK) ? rtk::kVarStats : 0) | (fs.grid ? rtk::kVarGrid : 0) |
+         (fs.placement << rtk::kVarPlaceShift);
 }
 
 // How a render is cut into launches (render_enqueue; rt_internal_launch_plan
@@ -559,6 +531,53 @@ int pass_begin(rt_context *c, hipStream_t st, rt_frame_setup &fs) {
   return RT_OK;
 }
 
+// The layer grid's cell size for this frame geometry (rtk::grid_fitter: a
+// host-side model, once per geometry; the image is the same for every size).
+// The new grid is copied into the context's buffers on st, after every
+// earlier render (renders of one context are serialised), and written to kp.
+int refit_grid(rt_context *c, const rt_camera *cam, const rt_params *prm, hipStream_t st, rtk::kparams &kp) {
+  scene_state &s = c->sc;
+  std::vector<uint64_t> key = {(uint64_t)prm->width, (uint64_t)prm->height};
+  append_camera(key, cam);
+  if (key == s.fit_key) return RT_OK;
+  const double scale = s.fitter->choose(*cam, prm->width, prm->height, nullptr);
+  if (scale != s.grid.scale) {
+    if (s.fit_pending) RT_HIP(hipEventSynchronize(c->ev_fit));  // fit_grid is still being read
+    s.fit_pending = false;
+    rtk::grid_geom &q = s.fit_grid;
+    if (!s.fitter->build(scale, q)) return RT_ERR_INVALID;  // (every candidate fits: unreachable)
+    // Transactional: larger buffers are allocated before the
+    // old ones are freed, so a failed allocation leaves the old grid whole
+    // (buffers, fields and fit_key describe it); once a copy into the
+    // buffers has failed they hold neither grid, and grid_scale = NaN makes
+    // the next grid render refit before it launches.
+    if (q.cells.size() > s.d_grid_cells.cap || q.items.size() > s.d_grid_items.cap) {
+      rt_device_buf<uint32_t> cells;
+      rt_device_buf<float> items;
+      hipError_t ea = cells.grow(q.cells.size());
+      if (ea == hipSuccess) ea = items.grow(q.items.size());
+      if (ea == hipSuccess) ea = hipStreamSynchronize(st);  // earlier renders on st still read the old grid
+      if (ea != hipSuccess) return hip_fail(ea);
+      s.d_grid_cells = std::move(cells);  // (the old buffers are freed with these two)
+      s.d_grid_items = std::move(items);
+    }
+    s.grid.scale = std::numeric_limits<double>::quiet_NaN();
+    s.fit_key.clear();
+    RT_HIP(hipMemcpyAsync(s.d_grid_cells.p, q.cells.data(), q.cells.size() * sizeof(uint32_t),
+                          hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(s.d_grid_items.p, q.items.data(), q.items.size() * sizeof(float), hipMemcpyHostToDevice,
+                          st));
+    if (!c->ev_fit) RT_HIP(hipEventCreateWithFlags(&c->ev_fit, hipEventDisableTiming));
+    RT_HIP(hipEventRecord(c->ev_fit, st));
+    s.fit_pending = true;
+    s.grid_n_items = q.items.size() / 4;
+    s.grid = q;
+    grid_kparams(s, kp);
+  }
+  s.fit_key = key;
+  return RT_OK;
+}
+
 int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipStream_t st, rt_frame_setup &fs) {
   {
     const int r = pass_begin(c, st, fs);
@@ -567,64 +586,93 @@ int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipSt
   if (prm->width == 0 || prm->local_rows == 0) return RT_OK;  // nothing to launch
   rtk::kparams &kp = fs.kp;
   fill_kparams(c, cam, prm, nullptr, kp);
-  scene_state &s = c->sc;
-  const bool grid = s.d_grid_cells && !(prm->flags & RT_FLAG_LAYER_BVH);
+  const scene_state &s = c->sc;
+  // whether this pass walks the layer grid is decided here alone (fs.grid, fs.placement)
+  const bool grid = s.d_grid_cells.p && !(prm->flags & RT_FLAG_LAYER_BVH);
   if (grid && s.fitter && (prm->flags & RT_FLAG_ACCEL_BVH)) {
-    // the layer grid's cell size for this frame geometry (rtk::grid_fitter:
-    // a host-side model, once per geometry; the image is the same for every
-    // size).  The new grid is copied into the context's buffers on st, after
-    // every earlier render (renders of one context are serialised).
-    std::vector<uint64_t> key = {(uint64_t)prm->width, (uint64_t)prm->height};
-    append_camera(key, cam);
-    if (key != s.fit_key) {
-      const double scale = s.fitter->choose(*cam, prm->width, prm->height, nullptr);
-      if (scale != s.grid.scale) {
-        if (s.fit_pending) RT_HIP(hipEventSynchronize(c->ev_fit));  // fit_grid is still being read
-        s.fit_pending = false;
-        rtk::grid_geom &q = s.fit_grid;
-        if (!s.fitter->build(scale, q)) return RT_ERR_INVALID;  // (every candidate fits: unreachable)
-        // Transactional: larger buffers are allocated before the
-        // old ones are freed, so a failed allocation leaves the old grid whole
-        // (buffers, fields and fit_key describe it); once a copy into the
-        // buffers has failed they hold neither grid, and grid_scale = NaN makes
-        // the next grid render refit before it launches.
-        if (q.cells.size() > s.cells_cap || q.items.size() / 4 > s.items_cap) {
-          void *nc = nullptr, *ni = nullptr;
-          hipError_t ea = hipMalloc(&nc, q.cells.size() * sizeof(uint32_t));
-          if (ea == hipSuccess) ea = hipMalloc(&ni, q.items.size() * sizeof(float));
-          if (ea == hipSuccess) ea = hipStreamSynchronize(st);  // earlier renders on st still read the old grid
-          if (ea != hipSuccess) {
-            (void)hipFree(nc);
-            (void)hipFree(ni);
-            return hip_fail(ea);
-          }
-          (void)hipFree(s.d_grid_cells);
-          (void)hipFree(s.d_grid_items);
-          s.d_grid_cells = static_cast<uint32_t *>(nc);
-          s.d_grid_items = static_cast<float *>(ni);
-          s.cells_cap = q.cells.size();
-          s.items_cap = q.items.size() / 4;
-        }
-        s.grid.scale = std::numeric_limits<double>::quiet_NaN();
-        s.fit_key.clear();
-        RT_HIP(hipMemcpyAsync(s.d_grid_cells, q.cells.data(), q.cells.size() * sizeof(uint32_t),
-                              hipMemcpyHostToDevice, st));
-        RT_HIP(hipMemcpyAsync(s.d_grid_items, q.items.data(), q.items.size() * sizeof(float), hipMemcpyHostToDevice,
-                              st));
-        if (!c->ev_fit) RT_HIP(hipEventCreateWithFlags(&c->ev_fit, hipEventDisableTiming));
-        RT_HIP(hipEventRecord(c->ev_fit, st));
-        s.fit_pending = true;
-        s.grid_n_items = q.items.size() / 4;
-        s.grid = q;
-        grid_kparams(s.grid, s.d_grid_cells, s.d_grid_items, s.grid_n_items, kp);
-      }
-      s.fit_key = key;
-    }
+    const int r = refit_grid(c, cam, prm, st, kp);
+    if (r != RT_OK) return r;
   }
   fs.grid = grid ? 1 : 0;
   fs.placement = grid ? s.grid_placement : rtk::kGridGlobal;
   fs.lds_bytes = rtk::grid_lds_bytes(fs.placement, kp.grid_n_items, kp.grid_n_cells);
   return RT_OK;
+}
+
+// Expensive tiles first (RT_FLAG_PILOT_SCHEDULE): a 4-spp pilot (same
+// geometry, one wave per tile, the instrumented build that reports each
+// tile's segments) runs once per frame geometry; blocks are then launched
+// in decreasing cost of their tiles (longest-processing-time first), the
+// units of a tile group adjacent.  Without it the hardware launches
+// blocks in index order and the last wave slots to fill may get the most
+// expensive tiles.  Scheduling only: the image does not depend on it.
+// Everything stays on st (the sort runs on the device, rt_sched.hip).
+// kp, v: the render's arguments and variant; *order = the context's block order.
+hipError_t pilot_order(rt_context *c, const rt_camera *cam, const rt_params *prm, const rtk::kparams &kp, int v,
+                       unsigned blocks, long long units, hipStream_t st, const uint32_t **order) {
+  std::vector<uint64_t> key = {(uint64_t)prm->width, (uint64_t)prm->height, (uint64_t)prm->local_rows,
+                               (uint64_t)prm->row_block, (uint64_t)prm->band_stride,
+                               (uint64_t)prm->band_offset, (uint64_t)units, (uint64_t)(prm->flags & 0x12ffu)};
+  append_camera(key, cam);
+  if (key != c->order_key || c->order_n != (size_t)blocks * units) {
+    c->order_key.clear();  // valid again only once the new order is enqueued
+    // tile costs, then 8 scratch counters (the context's are not touched)
+    const size_t n_cost = (size_t)blocks * rtk::kWavesPerBlock;
+    const size_t cost_bytes = (n_cost * sizeof(uint32_t) + 7) / 8 * 8;
+    uint32_t *d_cost = nullptr;
+    hipError_t e = hipMallocAsync((void **)&d_cost, cost_bytes + 8 * sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(d_cost, 0, cost_bytes + 8 * sizeof(unsigned long long), st);
+    if (e == hipSuccess) {
+      // the instrumented build with the grid in global memory, 4 samples,
+      // one unit, float stores
+      rtk::kparams pk = kp;
+      pk.s_lo = 0;
+      pk.s_cnt = std::min(prm->spp, 4);
+      pk.units = 1;
+      pk.sum_atomic = 0;
+      pk.tile_cost = d_cost;
+      pk.counters = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(d_cost) + cost_bytes);
+      e = rtk::launch_render((v & ~(3 << rtk::kVarPlaceShift)) | rtk::kVarStats, blocks, 0, st, pk);
+    }
+    if (e == hipSuccess && c->d_order) e = hipFreeAsync(c->d_order, st);
+    if (e == hipSuccess) {
+      c->d_order = nullptr;
+      c->order_n = 0;
+      e = hipMallocAsync((void **)&c->d_order, (size_t)blocks * units * sizeof(uint32_t), st);
+    }
+    if (e == hipSuccess) e = rt_internal_block_order(d_cost, blocks, (uint32_t)units, c->d_order, st);
+    (void)hipFreeAsync(d_cost, st);  // also on error: no leak
+    if (e != hipSuccess) return e;
+    c->order_n = (size_t)blocks * units;
+    c->order_key = key;
+  }
+  *order = c->d_order;
+  return hipSuccess;
+}
+
+// Where the launches leave a pixel's sum.  One launch and one unit per tile:
+// float stores into the caller's frame.  Several units or launches per tile add
+// their integer sums into a zeroed frame, which finish_sums converts at the end:
+// the caller's, or, for 64-bit sums, which do not fit its fp32 frame, a scratch
+// frame of the context's (renders of one context are serialised).
+enum sum_target { kSumStore, kSumAtomic, kSumAtomicWide };
+
+hipError_t begin_sums(rt_context *c, sum_target t, float *accum_rgb, uint64_t frame_floats, hipStream_t st,
+                      rtk::kparams &kp) {
+  if (t == kSumStore) return hipSuccess;
+  if (t == kSumAtomic) return hipMemsetAsync(accum_rgb, 0, frame_floats * sizeof(float), st);
+  hipError_t e = c->d_wide.grow(frame_floats);
+  if (e == hipSuccess) e = hipMemsetAsync(c->d_wide.p, 0, frame_floats * sizeof(uint64_t), st);
+  if (e == hipSuccess) kp.out = reinterpret_cast<float *>(c->d_wide.p);
+  return e;
+}
+
+hipError_t end_sums(rt_context *c, sum_target t, float *accum_rgb, uint64_t frame_floats, float qinv,
+                    hipStream_t st) {
+  if (t == kSumStore) return hipSuccess;
+  if (t == kSumAtomic) return rtk::launch_finish_sums(reinterpret_cast<uint32_t *>(accum_rgb), frame_floats, qinv, st);
+  return rtk::launch_finish_sums_wide(c->d_wide.p, accum_rgb, frame_floats, qinv, st);
 }
 
 // rt_render_async's body (stream NULL: the context's own).  ev_start (may be
@@ -644,7 +692,7 @@ int render_enqueue(rt_context *c, const rt_camera *cam, const rt_params *prm, fl
   if (prm->flags & RT_FLAG_KEEP_COUNTERS) {
     c->last_samples += samples;
   } else {
-    RT_HIP(hipMemsetAsync(c->d_counters, 0, 8 * rtk::kCounterSlots * sizeof(unsigned long long), st));
+    RT_HIP(hipMemsetAsync(c->d_counters.p, 0, 8 * rtk::kCounterSlots * sizeof(unsigned long long), st));
     c->last_samples = samples;
     c->last_launches = 0;
   }
@@ -659,132 +707,45 @@ int render_enqueue(rt_context *c, const rt_camera *cam, const rt_params *prm, fl
   kp.out = accum_rgb;
   const unsigned blocks = (unsigned)rt_frame_blocks(prm);
   const sum_fmt fmt = sum_format(prm->spp, prm->max_depth, c->sc.max_albedo);
-  const int v = render_variant(c, prm, fmt.wide);
-  const size_t lds = fs.lds_bytes;
+  sum_kparams(fmt, kp);
+  const int v = render_variant(fs, prm, fmt.wide);
   const bool traced = prm->spp > 0 && prm->max_depth > 0;
   const launch_plan lp = plan_launches(prm, c->launch_samples);
-  const long long units = lp.units, ranges = lp.ranges, chunks = lp.chunks, entries = lp.entries;
-  const long long launches = ranges * chunks;
-  kp.units = (int)units;
-  const int f = fmt.f;
-  kp.qscale = std::ldexp(1.0f, f);
-  kp.qinv = std::ldexp(1.0f, -f);
-  kp.vcap = fmt.vcap;
-  // F < 20 (spp >= 4096): truncation would bias a dark pixel by up to 2^-F per
-  // sample (0.03 level at F = 20); stochastic rounding is unbiased for every
-  // spp (DESIGN.md 2, step 6)
-  kp.dither = f < 20 ? 1 : 0;
+  const long long launches = lp.ranges * lp.chunks;
+  kp.units = (int)lp.units;
   // disjoint block ranges write disjoint pixels: float stores suffice
-  kp.sum_atomic = (units > 1 || chunks > 1) ? 1 : 0;
+  const sum_target sums = !(lp.units > 1 || lp.chunks > 1) ? kSumStore : fmt.wide ? kSumAtomicWide : kSumAtomic;
+  kp.sum_atomic = sums != kSumStore ? 1 : 0;
   const uint64_t frame_floats = (uint64_t)prm->local_rows * (uint64_t)prm->width * 3u;
-  if ((prm->flags & RT_FLAG_PILOT_SCHEDULE) && traced && blocks > 1) {
-    // Expensive tiles first (RT_FLAG_PILOT_SCHEDULE): a 4-spp pilot (same
-    // geometry, one wave per tile, the instrumented build that reports each
-    // tile's segments) runs once per frame geometry; blocks are then launched
-    // in decreasing cost of their tiles (longest-processing-time first), the
-    // units of a tile group adjacent.  Without it the hardware launches
-    // blocks in index order and the last wave slots to fill may get the most
-    // expensive tiles.  Scheduling only: the image does not depend on it.
-    // Everything stays on st (the sort runs on the device, rt_sched.hip).
-    std::vector<uint64_t> key = {(uint64_t)prm->width, (uint64_t)prm->height, (uint64_t)prm->local_rows,
-                                 (uint64_t)prm->row_block, (uint64_t)prm->band_stride,
-                                 (uint64_t)prm->band_offset, (uint64_t)units, (uint64_t)(prm->flags & 0x12ffu)};
-    append_camera(key, cam);
-    if (key != c->order_key || c->order_n != (size_t)blocks * units) {
-      c->order_key.clear();  // valid again only once the new order is enqueued
-      // tile costs, then 8 scratch counters (the context's are not touched)
-      const size_t n_cost = (size_t)blocks * rtk::kWavesPerBlock;
-      const size_t cost_bytes = (n_cost * sizeof(uint32_t) + 7) / 8 * 8;
-      uint32_t *d_cost = nullptr;
-      RT_HIP(hipMallocAsync((void **)&d_cost, cost_bytes + 8 * sizeof(unsigned long long), st));
-      hipError_t e = hipMemsetAsync(d_cost, 0, cost_bytes + 8 * sizeof(unsigned long long), st);
-      if (e == hipSuccess) {
-        // the instrumented build with the grid in global memory, 4 samples,
-        // one unit, float stores
-        rtk::kparams pk = kp;
-        pk.s_lo = 0;
-        pk.s_cnt = std::min(prm->spp, 4);
-        pk.units = 1;
-        pk.sum_atomic = 0;
-        pk.tile_cost = d_cost;
-        pk.counters = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(d_cost) + cost_bytes);
-        e = rtk::launch_render((v & ~(3 << rtk::kVarPlaceShift)) | rtk::kVarStats, blocks, 0, st, pk);
-      }
-      if (e == hipSuccess && c->d_order) e = hipFreeAsync(c->d_order, st);
-      if (e == hipSuccess) {
-        c->d_order = nullptr;
-        c->order_n = 0;
-        e = hipMallocAsync((void **)&c->d_order, (size_t)blocks * units * sizeof(uint32_t), st);
-      }
-      if (e == hipSuccess) e = rt_internal_block_order(d_cost, blocks, (uint32_t)units, c->d_order, st);
-      (void)hipFreeAsync(d_cost, st);  // also on error: no leak
-      if (e != hipSuccess) return hip_fail(e);
-      c->order_n = (size_t)blocks * units;
-      c->order_key = key;
-    }
-    kp.block_order = c->d_order;
-  }
-  // several units or launches per tile add their integer sums into the
-  // zeroed frame (after the pilot, which renders into it too); finish_sums
-  // converts them
-  if (kp.sum_atomic && fmt.wide) {
-    // 64-bit sums do not fit the caller's fp32 frame: a scratch frame of the
-    // context's (renders of one context are serialised), converted at the end
-    if (c->wide_n < frame_floats) {
-      (void)hipFree(c->d_wide);
-      c->d_wide = nullptr;
-      c->wide_n = 0;
-      RT_HIP(hipMalloc(&c->d_wide, frame_floats * sizeof(uint64_t)));
-      c->wide_n = frame_floats;
-    }
-    RT_HIP(hipMemsetAsync(c->d_wide, 0, frame_floats * sizeof(uint64_t), st));
-    kp.out = reinterpret_cast<float *>(c->d_wide);
-  } else if (kp.sum_atomic) {
-    RT_HIP(hipMemsetAsync(accum_rgb, 0, frame_floats * sizeof(float), st));
-  }
-  {
-    while (c->ev_launch.size() < (size_t)launches) {
-      hipEvent_t ev = nullptr;
-      RT_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      c->ev_launch.push_back(ev);
-    }
+  if ((prm->flags & RT_FLAG_PILOT_SCHEDULE) && traced && blocks > 1)
+    RT_HIP(pilot_order(c, cam, prm, kp, v, blocks, lp.units, st, &kp.block_order));
+  RT_HIP(begin_sums(c, sums, accum_rgb, frame_floats, st, kp));  // (after the pilot, which renders into accum_rgb too)
+  while (c->ev_launch.size() < (size_t)launches) {  // one event per bounded launch (the pool only grows)
+    hipEvent_t ev = nullptr;
+    RT_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    c->ev_launch.push_back(ev);
   }
   if (ev_start) RT_HIP(hipEventRecord(ev_start, st));
   long long k = 0;
-  kp.block_stride = (int)ranges;
-  for (long long r = 0; r < ranges; ++r) {
+  kp.block_stride = (int)lp.ranges;
+  for (long long r = 0; r < lp.ranges; ++r) {
     // entries r, r + ranges, r + 2 ranges, ... in block_order's order (most
     // expensive first with the pilot)
     kp.block_base = (int)r;
-    const long long n_r = (entries - r + ranges - 1) / ranges;
-    for (long long ch = 0; ch < chunks; ++ch, ++k) {
-      const long long s0 = ch * prm->spp / chunks, s1 = (ch + 1) * prm->spp / chunks;
+    const long long n_r = (lp.entries - r + lp.ranges - 1) / lp.ranges;
+    for (long long ch = 0; ch < lp.chunks; ++ch, ++k) {
+      const long long s0 = ch * prm->spp / lp.chunks, s1 = (ch + 1) * prm->spp / lp.chunks;
       kp.s_lo = (int)s0;
       kp.s_cnt = (int)(s1 - s0);
       // a launch that cannot start (bad configuration, lost device) stops the render here
-      RT_HIP(rtk::launch_render(v, (unsigned)n_r, lds, st, kp));
+      RT_HIP(rtk::launch_render(v, (unsigned)n_r, fs.lds_bytes, st, kp));
       RT_HIP(hipEventRecord(c->ev_launch[(size_t)k], st));
     }
   }
   c->last_launches += (uint32_t)launches;
   c->enq_launches = (uint32_t)launches;
-  if (kp.sum_atomic && fmt.wide)
-    RT_HIP(rtk::launch_finish_sums_wide(c->d_wide, accum_rgb, frame_floats, kp.qinv, st));
-  else if (kp.sum_atomic)
-    RT_HIP(rtk::launch_finish_sums(reinterpret_cast<uint32_t *>(accum_rgb), frame_floats, kp.qinv, st));
+  RT_HIP(end_sums(c, sums, accum_rgb, frame_floats, kp.qinv, st));
   return ps.end(RT_OK);
-}
-
-// rt_render's frame buffer (only it uses d_frame, and it returns after its
-// work is done)
-hipError_t ensure_frame(rt_context *c, size_t nf) {
-  if (nf <= c->frame_floats) return hipSuccess;
-  (void)hipFree(c->d_frame);
-  c->d_frame = nullptr;
-  c->frame_floats = 0;
-  const hipError_t e = hipMalloc(&c->d_frame, nf * sizeof(float));
-  if (e == hipSuccess) c->frame_floats = nf;
-  return e;
 }
 
 }  // namespace
@@ -795,7 +756,7 @@ int rt_internal_frame_check(const rt_context *c, const rt_camera *cam, const rt_
   if (!c || !cam || !params_ok(prm)) return RT_ERR_INVALID;
   if (cam->model != RT_CAMERA_CPU && cam->model != RT_CAMERA_GPU) return RT_ERR_INVALID;
   if (cam->model == RT_CAMERA_CPU && (prm->width < 2 || prm->height < 2)) return RT_ERR_INVALID;
-  if (!c->sc.d_geom) return RT_ERR_NO_SCENE;
+  if (!c->sc.d_geom.p) return RT_ERR_NO_SCENE;
   return RT_OK;
 }
 
@@ -846,7 +807,7 @@ int rt_render_progress(rt_context *c, uint32_t *done, uint32_t *total) {
 int rt_reset_stats(rt_context *c, void *stream) {
   if (!c) return RT_ERR_INVALID;
   RT_HIP(hipSetDevice(c->device));
-  RT_HIP(hipMemsetAsync(c->d_counters, 0, 8 * rtk::kCounterSlots * sizeof(unsigned long long),
+  RT_HIP(hipMemsetAsync(c->d_counters.p, 0, 8 * rtk::kCounterSlots * sizeof(unsigned long long),
                         stream ? (hipStream_t)stream : c->stream));
   c->last_samples = 0;
   c->last_launches = 0;
@@ -857,12 +818,12 @@ int rt_collect_stats(rt_context *c, rt_stats *stats) {
   if (!c || !stats) return RT_ERR_INVALID;
   unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hs[8 * rtk::kCounterSlots];
   RT_HIP(hipSetDevice(c->device));
-  RT_HIP(hipMemcpy(hs, c->d_counters, sizeof hs, hipMemcpyDeviceToHost));
+  RT_HIP(hipMemcpy(hs, c->d_counters.p, sizeof hs, hipMemcpyDeviceToHost));
   for (int i = 0; i < 8 * rtk::kCounterSlots; ++i) h[i & 7] += hs[i];
   stats->segments = h[0];
   stats->wave_steps = h[1];
   stats->samples = c->last_samples;
-  stats->bf_tests = h[0] * (uint64_t)c->sc.n_spheres;
+  stats->bf_tests = h[0] * (uint64_t)c->sc.dims.n;
   stats->sphere_tests = c->last_stats ? h[2] : 0;
   stats->box_tests = c->last_stats ? h[3] : 0;
   stats->box_hits = c->last_stats ? h[4] : 0;
@@ -879,9 +840,9 @@ int rt_render(rt_context *c, const rt_camera *cam, const rt_params *prm, float *
   if (st != RT_OK) return st;
   const size_t nf = 3 * (size_t)prm->width * (size_t)prm->local_rows;
   RT_HIP(hipSetDevice(c->device));
-  RT_HIP(ensure_frame(c, nf));
+  RT_HIP(c->d_frame.grow(nf));
   // ev0 is recorded right before the render kernel (after a first-frame pilot)
-  st = render_enqueue(c, cam, prm, c->d_frame, nullptr, c->ev0);
+  st = render_enqueue(c, cam, prm, c->d_frame.p, nullptr, c->ev0);
   const uint32_t n_launch = std::min<uint32_t>(c->enq_launches, (uint32_t)c->ev_launch.size());
   if (st != RT_OK) return st;
   RT_HIP(hipEventRecord(c->ev1, c->stream));
@@ -890,7 +851,7 @@ int rt_render(rt_context *c, const rt_camera *cam, const rt_params *prm, float *
   RT_HIP(hipEventSynchronize(c->ev1));
   float ms = 0.f;
   RT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  if (nf) RT_HIP(hipMemcpy(host_rgb, c->d_frame, nf * sizeof(float), hipMemcpyDeviceToHost));
+  if (nf) RT_HIP(hipMemcpy(host_rgb, c->d_frame.p, nf * sizeof(float), hipMemcpyDeviceToHost));
   if (stats) {
     st = rt_collect_stats(c, stats);
     if (st != RT_OK) return st;
@@ -927,8 +888,8 @@ int rt_internal_accel_info(const rt_scene_view *s, int grid_placement, double gr
   rtk::build_accel(s, o, a);
   uint64_t v[RT_ACCEL_INFO_N];
   std::memset(v, 0, sizeof v);
-  v[0] = a.per_order;
-  v[1] = a.slots.size();
+  v[0] = a.per_order;  // (a's rtk::scene_dims)
+  v[1] = a.n_slots;
   v[2] = a.layer_mode ? 1u : 0u;
   v[3] = a.extra_pair0;
   v[4] = a.n_extra_pairs;
@@ -1003,7 +964,7 @@ int rt_internal_grid_fit_phase(const rt_scene_view *s, const rt_camera *cam, int
 
 int rt_internal_grid_scale(rt_context *c, double *scale) {
   if (!c || !scale) return RT_ERR_INVALID;
-  *scale = c->sc.d_grid_cells ? c->sc.grid.scale : 0.0;
+  *scale = c->sc.d_grid_cells.p ? c->sc.grid.scale : 0.0;
   return RT_OK;
 }
 
@@ -1042,9 +1003,9 @@ int rt_tonemap_async(rt_context *c, const float *d_sums, size_t n_pixels, int sp
   RT_HIP(hipSetDevice(c->device));
   const uint64_t n = 3 * (uint64_t)n_pixels;
   if (mode == RT_TONEMAP_CPU)
-    RT_HIP(rtk::launch_tonemap(false, d_sums, n, spp, c->d_thr64, d_out, st));
+    RT_HIP(rtk::launch_tonemap(false, d_sums, n, spp, c->d_thr64.p, d_out, st));
   else
-    RT_HIP(rtk::launch_tonemap(true, d_sums, n, spp, c->d_thr32, d_out, st));
+    RT_HIP(rtk::launch_tonemap(true, d_sums, n, spp, c->d_thr32.p, d_out, st));
   return RT_OK;
 }
 

@@ -2,15 +2,16 @@
 // rt_api.cpp, the first-hit feature pass in rt_aov.hip / librtow_aov.so), or a
 // pass that only shares the context's ordering (the denoiser in
 // rt_denoise.hip / librtow_denoise.so), starts and ends on a stream, and the
-// host helpers the three share (hip_fail / RT_HIP, rt_pass_scope, rt_staging).
-// Not installed; rt_context stays opaque outside rt_api.cpp, so the other
-// libraries get what they need through rt_frame_setup.
+// host helpers the three share (hip_fail / RT_HIP, rt_pass_scope,
+// rt_device_buf, rt_staging).  Not installed; rt_context stays opaque outside
+// rt_api.cpp, so the other libraries get what they need through rt_frame_setup.
 #ifndef RTOW_RT_FRAME_H
 #define RTOW_RT_FRAME_H
 
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <utility>
 
 #include "rt_layout.h"
 
@@ -99,6 +100,31 @@ struct rt_pass_scope {
  private:
   rt_context *c_;
   bool ended_ = false;
+};
+
+// A device buffer and its capacity in elements, freed with its owner (move
+// only).  grow(n): nothing when it already holds n elements, else the old
+// buffer is freed and a new one allocated (the contents are not kept); after
+// a failed allocation it holds nothing.
+template <class T>
+struct rt_device_buf {
+  T *p = nullptr;
+  size_t cap = 0;
+  rt_device_buf() = default;
+  rt_device_buf(rt_device_buf &&o) noexcept { *this = std::move(o); }
+  rt_device_buf &operator=(rt_device_buf &&o) noexcept {  // (o then frees what *this held)
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~rt_device_buf() { (void)hipFree(p); }
+  hipError_t grow(size_t n) {
+    if (n <= cap) return hipSuccess;
+    *this = rt_device_buf();
+    const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+    if (e == hipSuccess) cap = n;
+    return e;
+  }
 };
 
 // A synchronous wrapper's device buffers: 256-byte aligned parts of one

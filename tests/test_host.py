@@ -336,6 +336,30 @@ def test_accel_builder_invariants_on_host(rtow):
     assert five["layer_mode"] == 0 and five["grid_items"] == 0
 
 
+def test_accel_info_equals_the_recorded_values(rtow):
+    """Every value of rt_internal_accel_info (all RT_ACCEL_INFO_N: the scene's
+    scalar facts that become kernel arguments, the grid's dimensions and
+    placement, the extras' class and slots) for the final scene, the
+    10 000-sphere scene, the five-sphere scene and the extras scenes of
+    tests/extras_scenes.py equals tests/golden/accel_info.json, which was
+    recorded with the build before the builder's facts moved into one record
+    (rtk::scene_dims): the record carries each of them unchanged."""
+    import ctypes
+    import json
+    import extras_scenes
+    scenes = {"final": rtow.final_scene(), "final_50": rtow.final_scene(50), "five": rtow.five_scene()}
+    scenes.update(extras_scenes.random_with_extras(rtow))
+    scenes.update({name: sc for name, (sc, _) in extras_scenes.hand_made(rtow).items()})
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "accel_info.json")) as f:
+        want = json.load(f)
+    assert set(want) == set(scenes)
+    for name, scene in scenes.items():
+        v = scene.view()
+        out = np.zeros(36, np.uint64)  # RT_ACCEL_INFO_N
+        rtow.check(rtow.lib().rt_internal_accel_info(ctypes.byref(v), 0, 0.0, out.ctypes.data, out.size), name)
+        assert [int(x) for x in out] == want[name], name
+
+
 def test_grid_fit_picks_a_candidate_per_camera(rtow):
     """RT_OPT_GRID_FIT (rtk::grid_fitter, DESIGN.md 3.3): the host model of
     the layer walk's cost picks one of the builder's candidate cell scales
