@@ -26,6 +26,8 @@ LIB_PATH = os.environ.get("RTOW_LIB") or os.path.join(HERE, "librtow.so")
 AOV_LIB_PATH = os.path.join(HERE, "librtow_aov.so")
 # the guided a-trous denoiser (include/rt_denoise.h): a third library on the same terms
 DENOISE_LIB_PATH = os.path.join(HERE, "librtow_denoise.so")
+# temporal accumulation with camera reprojection (include/rt_temporal.h): a fourth
+TEMPORAL_LIB_PATH = os.path.join(HERE, "librtow_temporal.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
@@ -50,6 +52,10 @@ DENOISE_VERSION = 1  # include/rt_denoise.h RT_DENOISE_VERSION
 # rt_denoise_desc's input pointers in order, and its options with their defaults
 DENOISE_INPUTS = ("beauty", "hits", "position", "normal", "albedo")
 DENOISE_DEFAULTS = {"iterations": 5, "normal_power": 6, "sigma_plane": 0.5, "sigma_color": 0.15}
+TEMPORAL_VERSION = 1  # include/rt_temporal.h RT_TEMPORAL_VERSION
+# rt_temporal_desc's pointers in order (history_in and out may be NULL), and its options with their defaults
+TEMPORAL_BUFFERS = ("cur", "hits", "position", "normal", "history_in", "history_out", "out")
+TEMPORAL_DEFAULTS = {"max_len": 2, "plane_tol": 0.0003, "normal_cos": 0.9}
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
 RT_OPT_BVH_COLLAPSE, RT_OPT_BVH_SIDE, RT_OPT_LAUNCH_SAMPLES, RT_OPT_GRID_FIT = 4, 5, 6, 7
@@ -113,9 +119,90 @@ class DenoiseDesc(ctypes.Structure):
                 [(name, ctypes.c_void_p) for name in DENOISE_INPUTS + ("out",)])
 
 
+class TemporalView(ctypes.Structure):
+    """rt_temporal_view: world point -> continuous pixel coordinates of a frame."""
+    _fields_ = [(name, ctypes.c_float * 3) for name in ("eye", "px", "py", "pw")] + \
+               [("x0", ctypes.c_float), ("y0", ctypes.c_float)]
+
+
+class TemporalDesc(ctypes.Structure):
+    """rt_temporal_desc: the frame, the options (0 = default), the previous
+    frame's view and device (rt_temporal_async) or host (rt_temporal) pointers."""
+    _fields_ = ([(name, ctypes.c_int32) for name in ("width", "height", "spp", "max_len")] +
+                [("plane_tol", ctypes.c_float), ("normal_cos", ctypes.c_float), ("reserved", ctypes.c_int32 * 2),
+                 ("prev", TemporalView)] +
+                [(name, ctypes.c_void_p) for name in TEMPORAL_BUFFERS])
+
+
 _lib = None
 _aov_lib = None
 _denoise_lib = None
+_temporal_lib = None
+
+
+def temporal_lib():
+    """Load librtow_temporal.so, temporal accumulation with reprojection
+    (raises if it has not been built).  librtow.so loads first: the pass runs
+    on its contexts."""
+    global _temporal_lib
+    if _temporal_lib is None:
+        lib()
+        if not os.path.exists(TEMPORAL_LIB_PATH):
+            raise RuntimeError(f"{TEMPORAL_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or make -C ray-tracing-in-one-weekend_amd)")
+        L = ctypes.CDLL(TEMPORAL_LIB_PATH)
+        L.rt_temporal_version.restype = ctypes.c_int
+        L.rt_temporal_history_bytes.restype = ctypes.c_size_t
+        L.rt_temporal_history_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.rt_temporal_view_from_camera.argtypes = [ctypes.POINTER(Camera), ctypes.c_int, ctypes.c_int,
+                                                   ctypes.POINTER(TemporalView)]
+        L.rt_temporal_async.argtypes = [ctypes.c_void_p, ctypes.POINTER(TemporalDesc), ctypes.c_void_p]
+        L.rt_temporal.argtypes = [ctypes.c_void_p, ctypes.POINTER(TemporalDesc), ctypes.POINTER(ctypes.c_double)]
+        if L.rt_temporal_version() != TEMPORAL_VERSION:
+            raise RuntimeError(f"{TEMPORAL_LIB_PATH}: RT_TEMPORAL_VERSION {L.rt_temporal_version()}, "
+                               f"expected {TEMPORAL_VERSION}")
+        _temporal_lib = L
+    return _temporal_lib
+
+
+def temporal_view(cam, width, height):
+    """The TemporalView of a camera for a width x height frame
+    (rt_temporal_view_from_camera): what the NEXT frame's pass gets as prev."""
+    v = TemporalView()
+    check(temporal_lib().rt_temporal_view_from_camera(ctypes.byref(cam), width, height, ctypes.byref(v)),
+          "rt_temporal_view_from_camera")
+    return v
+
+
+def as_temporal_view(view):
+    """A TemporalView from anything with eye, px, py, pw (three numbers each), x0 and y0."""
+    if isinstance(view, TemporalView):
+        return view
+    v = TemporalView(x0=float(view.x0), y0=float(view.y0))
+    for name in ("eye", "px", "py", "pw"):
+        setattr(v, name, (ctypes.c_float * 3)(*[float(x) for x in getattr(view, name)]))
+    return v
+
+
+def temporal_desc(width, height, spp, prev_view=None, **options):
+    """A TemporalDesc without pointers.  Options (TEMPORAL_DEFAULTS) left out
+    or None take their defaults; a value means itself: plane_tol=inf and
+    normal_cos=-1 switch their tests off.  The struct reads 0 as "default", so
+    max_len=0, plane_tol=0 and normal_cos=0 cannot be asked for."""
+    unknown = [k for k in options if k not in TEMPORAL_DEFAULTS]
+    if unknown:
+        raise ValueError(f"unknown temporal options {unknown}")
+    opt = {k: v for k, v in options.items() if v is not None}
+    zero = [k for k, v in opt.items() if v == 0]
+    if zero:
+        raise ValueError(f"temporal options {zero} must not be 0 (the struct's 0 means the default)")
+    d = TemporalDesc(width=width, height=height, spp=spp)
+    d.max_len = int(opt.get("max_len", 0))
+    d.plane_tol = float(opt.get("plane_tol", 0.0))
+    d.normal_cos = float(opt.get("normal_cos", 0.0))
+    if prev_view is not None:
+        d.prev = as_temporal_view(prev_view)
+    return d
 
 
 def denoise_lib():
@@ -533,6 +620,57 @@ class Context:
             setattr(d, name, ptr)
         check(denoise_lib().rt_denoise_async(self._h, ctypes.byref(d), ctypes.c_void_p(scratch_ptr),
                                              ctypes.c_void_p(stream)), "rt_denoise_async")
+
+    def temporal(self, cur, aov, spp, prev_view=None, history=None, **options):
+        """Temporal accumulation with reprojection (rt_temporal,
+        include/rt_temporal.h), synchronously, on host arrays: cur (H, W, 3)
+        float32 sums of this frame (the render's or the denoiser's), aov the
+        dict Context.aov returns for this frame ("hits", "position", "normal"
+        are read), history the (3, H, W, 4) float32 array the previous
+        frame's call returned and prev_view that frame's temporal_view (both
+        None: no history).  Options: TEMPORAL_DEFAULTS (see temporal_desc).
+        Returns (out, history_out): the accumulated sums (H, W, 3) and this
+        frame's history; self.temporal_ms holds the launch's event time."""
+        if (history is None) != (prev_view is None):
+            raise ValueError("history and prev_view go together")
+        d = temporal_desc(int(np.shape(cur)[1]), int(np.shape(cur)[0]), spp, prev_view, **options)
+        missing = [k for k in TEMPORAL_BUFFERS[1:4] if k not in aov]
+        if missing:
+            raise ValueError(f"feature buffers {missing} are missing")
+        keep = {"cur": np.ascontiguousarray(cur, np.float32), "hits": np.ascontiguousarray(aov["hits"], np.uint32)}
+        for k in TEMPORAL_BUFFERS[2:4]:
+            keep[k] = np.ascontiguousarray(aov[k], np.float32)
+        shapes = {"hits": (d.height, d.width), "history_in": (3, d.height, d.width, 4)}
+        if history is not None:
+            keep["history_in"] = np.ascontiguousarray(history, np.float32)
+        for k, a in keep.items():
+            if a.shape != shapes.get(k, (d.height, d.width, 3)):
+                raise ValueError(f"{k}: shape {a.shape} does not match the {d.width} x {d.height} frame")
+            setattr(d, k, a.ctypes.data)
+        out = np.zeros((d.height, d.width, 3), np.float32)
+        history_out = np.zeros((3, d.height, d.width, 4), np.float32)
+        d.out, d.history_out = out.ctypes.data, history_out.ctypes.data
+        ms = ctypes.c_double()
+        check(temporal_lib().rt_temporal(self._h, ctypes.byref(d), ctypes.byref(ms)), "rt_temporal")
+        self.temporal_ms = ms.value
+        return out, history_out
+
+    def temporal_async(self, dev_ptrs, width, height, spp, prev_view, stream=0, **options):
+        """Enqueue the pass (rt_temporal_async) on raw device pointers (e.g.
+        torch tensor.data_ptr()): dev_ptrs maps TEMPORAL_BUFFERS to device
+        pointers ("history_in" and "out" may be left out or None, "out" may be
+        the cur buffer; the histories are
+        temporal_lib().rt_temporal_history_bytes(width, height) bytes each and
+        must not overlap); prev_view: the view history_in was made with (None
+        without one)."""
+        unknown = [k for k in dev_ptrs if k not in TEMPORAL_BUFFERS]
+        if unknown:
+            raise ValueError(f"unknown temporal buffers {unknown}")
+        d = temporal_desc(width, height, spp, prev_view, **options)
+        for name, ptr in dev_ptrs.items():
+            setattr(d, name, ptr)
+        check(temporal_lib().rt_temporal_async(self._h, ctypes.byref(d), ctypes.c_void_p(stream)),
+              "rt_temporal_async")
 
     def tonemap_async(self, dev_sums, n_pixels, spp, dev_out, mode=RT_TONEMAP_CPU, stream=0):
         """write_color on the device: fp32 sums -> bytes, both device pointers."""
