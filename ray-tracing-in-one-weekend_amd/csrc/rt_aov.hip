@@ -259,54 +259,37 @@ int aov_launches(const rt_frame_setup &fs, const rt_params *prm, const rt_aov_bu
 }
 
 // One pass.  host false: rt_aov_async (bufs are device pointers, nothing
-// waits).  Else rt_aov: bufs are host pointers; the pass runs into one device
-// allocation on the context's stream, timed by the context's events, and is
-// waited for launch by launch.  Whatever was enqueued, the pass ends with the
-// context's ev_done recorded on its stream (rt_pass_scope).
+// waits).  Else rt_aov: bufs are host pointers; the pass runs through
+// rt_sync_pass and is waited for launch by launch.  Whatever was enqueued, the
+// pass ends with the context's ev_done recorded on its stream (rt_pass_scope).
 int aov_pass(rt_context *c, const rt_camera *cam, const rt_params *prm, const rt_aov_buffers *bufs, void *stream,
              bool host, double *kernel_ms) {
   const size_t npx = (size_t)prm->width * (size_t)prm->local_rows;
-  void *const hp[6] = {bufs->hits, bufs->id, bufs->depth, bufs->position, bufs->normal, bufs->albedo};
-  const size_t bytes[6] = {4 * npx, 4 * npx, 4 * npx, 12 * npx, 12 * npx, 12 * npx};
-  rt_staging stage;  // rt_aov: the wanted buffers' parts of the allocation
-  size_t off[6] = {0, 0, 0, 0, 0, 0};
-  for (int k = 0; k < 6; ++k)
-    if (hp[k]) off[k] = stage.add(bytes[k]);
+  if (!host || npx == 0) {
+    rt_pass_scope ps(c, cam, prm, host ? nullptr : stream);
+    return ps.end(ps.status != RT_OK || npx == 0 ? ps.status : aov_launches(ps.fs, prm, bufs, nullptr));
+  }
+  // the wanted buffers
+  const rt_sync_part parts[6] = {{bufs->hits ? 4 * npx : 0, nullptr, bufs->hits},
+                                 {bufs->id ? 4 * npx : 0, nullptr, bufs->id},
+                                 {bufs->depth ? 4 * npx : 0, nullptr, bufs->depth},
+                                 {bufs->position ? 12 * npx : 0, nullptr, bufs->position},
+                                 {bufs->normal ? 12 * npx : 0, nullptr, bufs->normal},
+                                 {bufs->albedo ? 12 * npx : 0, nullptr, bufs->albedo}};
   std::vector<hipEvent_t> events;
-  rt_pass_scope ps(c, cam, prm, host ? nullptr : stream);  // (sets the device)
-  const rt_frame_setup &fs = ps.fs;
-  if (ps.status != RT_OK || npx == 0) return ps.end(ps.status);
-  if (!host) return ps.end(aov_launches(fs, prm, bufs, nullptr));
-  const auto enqueue = [&]() -> int {
-    RT_HIP(stage.alloc());
-    rt_aov_buffers dev;
-    dev.hits = hp[0] ? stage.at<uint32_t>(off[0]) : nullptr;
-    dev.id = hp[1] ? stage.at<int32_t>(off[1]) : nullptr;
-    dev.depth = hp[2] ? stage.at<float>(off[2]) : nullptr;
-    dev.position = hp[3] ? stage.at<float>(off[3]) : nullptr;
-    dev.normal = hp[4] ? stage.at<float>(off[4]) : nullptr;
-    dev.albedo = hp[5] ? stage.at<float>(off[5]) : nullptr;
-    RT_HIP(hipEventRecord(fs.ev0, fs.stream));
-    const int r = aov_launches(fs, prm, &dev, &events);
-    if (r == RT_OK) RT_HIP(hipEventRecord(fs.ev1, fs.stream));
-    return r;
-  };
-  const auto collect = [&]() -> int {
-    // wait launch by launch: a fault surfaces after the launch it happened in
-    for (hipEvent_t ev : events) RT_HIP(hipEventSynchronize(ev));
-    RT_HIP(hipEventSynchronize(fs.ev1));
-    float ms = 0.0f;
-    RT_HIP(hipEventElapsedTime(&ms, fs.ev0, fs.ev1));
-    for (int k = 0; k < 6; ++k)
-      if (hp[k]) RT_HIP(hipMemcpy(hp[k], stage.at<char>(off[k]), bytes[k], hipMemcpyDeviceToHost));
-    if (kernel_ms) *kernel_ms = ms;
-    return RT_OK;
-  };
-  int r = ps.end(enqueue());
-  if (r == RT_OK)
-    r = collect();
-  else
-    (void)hipStreamSynchronize(fs.stream);  // launches may still write the buffers
+  const int r = rt_sync_pass(
+      c, cam, prm, parts, kernel_ms,
+      [&](void *const *dev, const rt_frame_setup &fs) {
+        const rt_aov_buffers d = {static_cast<uint32_t *>(dev[0]), static_cast<int32_t *>(dev[1]),
+                                  static_cast<float *>(dev[2]),    static_cast<float *>(dev[3]),
+                                  static_cast<float *>(dev[4]),    static_cast<float *>(dev[5])};
+        return aov_launches(fs, prm, &d, &events);
+      },
+      [&]() -> int {
+        // wait launch by launch: a fault surfaces after the launch it happened in
+        for (hipEvent_t ev : events) RT_HIP(hipEventSynchronize(ev));
+        return RT_OK;
+      });
   for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
   return r;
 }

@@ -15,7 +15,8 @@
 // A library of its own, like librtow_aov.so: librtow.so's
 // device code stays byte for byte what the committed PMC summaries were
 // collected on.  rt_api.cpp's rt_internal_pass_begin / rt_internal_frame_end
-// (csrc/rt_frame.h) keep the filter serialised with the context's renders.
+// (csrc/rt_frame.h) keep the filter serialised with the context's renders;
+// what it shares with rt_temporal.hip on the device is csrc/rt_post.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -25,17 +26,10 @@
 
 #include "rt_denoise.h"
 #include "rt_frame.h"
+#include "rt_post.h"
 
 namespace rtk {
 
-#define RT_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ RT_GLOBAL T *as_global(T *p) {
-  return (RT_GLOBAL T *)p;
-}
-
-constexpr int kDnTile = 16;  // 16 x 16 pixels per block: a wave is 16 x 4, its rows 256-byte runs of a plane
-constexpr int kDnMaxDim = 32768;
 constexpr float kDnDefaultSigmaPlane = 0.5f, kDnDefaultSigmaColor = 0.15f;
 constexpr int kDnDefaultIterations = 5, kDnDefaultNormalPower = 6;
 
@@ -60,10 +54,6 @@ struct dn_params {
   float sigma2;  // (sigma_color * 2^-i)^2; 0 = the colour term is off
 };
 
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-  return (ax * bx + ay * by) + az * bz;
-}
-
 // max(a_c, 1e-3f) of the header: the albedo the colour is divided by before
 // the filter and multiplied by after it
 __device__ __forceinline__ float demod(float albedo_sum, uint32_t h, int spp, float spp_f) {
@@ -79,24 +69,19 @@ __global__ __launch_bounds__(256) void prepare_kernel(const dn_params a) {
   const RT_GLOBAL float *g_n = as_global(a.normal) + 3 * o;
   const RT_GLOBAL float *g_a = as_global(a.albedo) + 3 * o;
   const uint32_t h = as_global(a.hits)[o];
-  const bool sky = h == 0;
-  const float hf = (float)h;
+  const post_guide g = post_prepare(h, g_p, g_n);
   f4 u, n, p;
   u.x = (g_b[0] / a.spp_f) / demod(g_a[0], h, a.spp, a.spp_f);
   u.y = (g_b[1] / a.spp_f) / demod(g_a[1], h, a.spp, a.spp_f);
   u.z = (g_b[2] / a.spp_f) / demod(g_a[2], h, a.spp, a.spp_f);
   u.w = 0.0f;
-  const float nx = g_n[0] / hf, ny = g_n[1] / hf, nz = g_n[2] / hf;
-  const float nn = dot3(nx, ny, nz, nx, ny, nz);
-  const float len = __builtin_sqrtf(nn);
-  const bool unit = !sky && nn > 0.0f;
-  n.x = unit ? nx / len : 0.0f;
-  n.y = unit ? ny / len : 0.0f;
-  n.z = unit ? nz / len : 0.0f;
-  n.w = sky ? 1.0f : 0.0f;
-  p.x = sky ? 0.0f : g_p[0] / hf;
-  p.y = sky ? 0.0f : g_p[1] / hf;
-  p.z = sky ? 0.0f : g_p[2] / hf;
+  n.x = g.nx;
+  n.y = g.ny;
+  n.z = g.nz;
+  n.w = g.sky ? 1.0f : 0.0f;
+  p.x = g.px;
+  p.y = g.py;
+  p.z = g.pz;
   p.w = 0.0f;
   as_global(a.guide_n)[o] = n;
   as_global(a.guide_p)[o] = p;
@@ -110,9 +95,8 @@ __global__ __launch_bounds__(256) void prepare_kernel(const dn_params a) {
 // 256-byte runs (every step).
 template <bool LAST>
 __global__ __launch_bounds__(256) void atrous_kernel(const dn_params a) {
-  const int x = (int)blockIdx.x * kDnTile + (int)(threadIdx.x & (kDnTile - 1));
-  const int y = (int)blockIdx.y * kDnTile + (int)(threadIdx.x / kDnTile);
-  if (x >= a.width || y >= a.height) return;
+  int x, y;
+  if (!post_pixel(a.width, a.height, x, y)) return;
   const size_t o = (size_t)y * (size_t)a.width + (size_t)x;
   const RT_GLOBAL f4 *__restrict__ gn = as_global(a.guide_n);
   const RT_GLOBAL f4 *__restrict__ gp = as_global(a.guide_p);
@@ -142,15 +126,15 @@ __global__ __launch_bounds__(256) void atrous_kernel(const dn_params a) {
       const f4 nq = gn[q], pq = gp[q], uq = src[q];
       const bool sky_q = nq.w != 0.0f;
       // w_n
-      float wn = dot3(np.x, np.y, np.z, nq.x, nq.y, nq.z);
+      float wn = dot3_unfused(np.x, np.y, np.z, nq.x, nq.y, nq.z);
       wn = wn > 0.0f ? wn : 0.0f;
       for (int i = 0; i < a.normal_power; ++i) wn = wn * wn;
       wn = sky_p != sky_q ? 0.0f : wn;
       wn = sky_p && sky_q ? 1.0f : wn;
       // w_p
       const float ex = pq.x - pp.x, ey = pq.y - pp.y, ez = pq.z - pp.z;
-      const float dd = dot3(ex, ey, ez, ex, ey, ez);
-      const float nd = dot3(np.x, np.y, np.z, ex, ey, ez);
+      const float dd = dot3_unfused(ex, ey, ez, ex, ey, ez);
+      const float nd = dot3_unfused(np.x, np.y, np.z, ex, ey, ez);
       float wp = 1.0f - (__builtin_fabsf(nd) / __builtin_sqrtf(dd)) / a.sigma_plane;
       wp = wp > 0.0f ? wp : 0.0f;
       wp = dd > 0.0f ? wp : 1.0f;
@@ -195,7 +179,7 @@ struct dn_options {
 };
 
 bool resolve(const rt_denoise_desc *d, dn_options &o) {
-  if (d->width < 1 || d->height < 1 || d->width > rtk::kDnMaxDim || d->height > rtk::kDnMaxDim) return false;
+  if (!rtk::post_size_ok(d->width, d->height)) return false;
   if (d->spp < 1 || d->reserved != 0) return false;
   if (!d->beauty || !d->hits || !d->position || !d->normal || !d->albedo || !d->out) return false;
   o.iterations = d->iterations == 0 ? rtk::kDnDefaultIterations : d->iterations;
@@ -237,8 +221,7 @@ int enqueue(const rt_denoise_desc *d, const dn_options &o, void *scratch, hipStr
   const size_t npx = (size_t)d->width * (size_t)d->height;
   rtk::prepare_kernel<<<(unsigned)((npx + 255) / 256), 256, 0, st>>>(a);
   RT_HIP(hipGetLastError());
-  const dim3 grid((unsigned)((d->width + rtk::kDnTile - 1) / rtk::kDnTile),
-                  (unsigned)((d->height + rtk::kDnTile - 1) / rtk::kDnTile));
+  const dim3 grid = rtk::post_grid(d->width, d->height);
   for (int i = 0; i < o.iterations; ++i) {
     a.src = plane[i & 1];
     a.dst = plane[(i + 1) & 1];
@@ -263,7 +246,7 @@ extern "C" {
 int rt_denoise_version(void) { return RT_DENOISE_VERSION; }
 
 size_t rt_denoise_scratch_bytes(int width, int height) {
-  if (width < 1 || height < 1 || width > rtk::kDnMaxDim || height > rtk::kDnMaxDim) return 0;
+  if (!rtk::post_size_ok(width, height)) return 0;
   return 4 * plane_bytes(width, height);
 }
 
@@ -277,46 +260,21 @@ int rt_denoise_async(rt_context *c, const rt_denoise_desc *d, void *scratch, voi
 int rt_denoise(rt_context *c, const rt_denoise_desc *host, double *kernel_ms) {
   dn_options o;
   if (!c || !host || !resolve(host, o)) return RT_ERR_INVALID;
-  if (kernel_ms) *kernel_ms = 0.0;
   const size_t npx = (size_t)host->width * (size_t)host->height;
-  // one allocation: beauty / out (filtered in place), hits, position, normal,
-  // albedo, then the scratch; every part 256-byte aligned
-  const void *hp[5] = {host->beauty, host->hits, host->position, host->normal, host->albedo};
-  const size_t bytes[5] = {12 * npx, 4 * npx, 12 * npx, 12 * npx, 12 * npx};
-  rt_staging stage;
-  size_t off[6];
-  for (int k = 0; k < 5; ++k) off[k] = stage.add(bytes[k]);
-  off[5] = stage.add(rt_denoise_scratch_bytes(host->width, host->height));
-  rt_pass_scope ps(c, nullptr, nullptr, nullptr);  // (sets the device)
-  const rt_frame_setup &fs = ps.fs;
-  const auto run = [&]() -> int {
-    if (ps.status != RT_OK) return ps.status;
-    RT_HIP(stage.alloc());
-    for (int k = 0; k < 5; ++k)
-      RT_HIP(hipMemcpyAsync(stage.at<char>(off[k]), hp[k], bytes[k], hipMemcpyHostToDevice, fs.stream));
-    RT_HIP(hipEventRecord(fs.ev0, fs.stream));
-    rt_denoise_desc dev = *host;
-    dev.beauty = dev.out = stage.at<float>(off[0]);
-    dev.hits = stage.at<uint32_t>(off[1]);
-    dev.position = stage.at<float>(off[2]);
-    dev.normal = stage.at<float>(off[3]);
-    dev.albedo = stage.at<float>(off[4]);
-    const int r = enqueue(&dev, o, stage.at<char>(off[5]), fs.stream);
-    if (r == RT_OK) RT_HIP(hipEventRecord(fs.ev1, fs.stream));
-    return r;
-  };
-  int r = ps.end(run());
-  if (fs.stream) {
-    // whatever was enqueued reads the host arrays and the allocation: wait
-    const hipError_t es = hipStreamSynchronize(fs.stream);
-    if (r == RT_OK && es != hipSuccess) r = hip_fail(es);
-  }
-  if (r != RT_OK) return r;
-  float ms = 0.0f;
-  RT_HIP(hipEventElapsedTime(&ms, fs.ev0, fs.ev1));
-  RT_HIP(hipMemcpy(host->out, stage.at<char>(off[0]), bytes[0], hipMemcpyDeviceToHost));
-  if (kernel_ms) *kernel_ms = ms;
-  return RT_OK;
+  // beauty / out (filtered in place), hits, position, normal, albedo, the scratch
+  const rt_sync_part parts[6] = {{12 * npx, host->beauty, host->out}, {4 * npx, host->hits, nullptr},
+                                 {12 * npx, host->position, nullptr}, {12 * npx, host->normal, nullptr},
+                                 {12 * npx, host->albedo, nullptr},
+                                 {rt_denoise_scratch_bytes(host->width, host->height), nullptr, nullptr}};
+  return rt_sync_pass(c, nullptr, nullptr, parts, kernel_ms, [&](void *const *dev, const rt_frame_setup &fs) {
+    rt_denoise_desc d = *host;
+    d.beauty = d.out = static_cast<float *>(dev[0]);
+    d.hits = static_cast<uint32_t *>(dev[1]);
+    d.position = static_cast<float *>(dev[2]);
+    d.normal = static_cast<float *>(dev[3]);
+    d.albedo = static_cast<float *>(dev[4]);
+    return enqueue(&d, o, dev[5], fs.stream);
+  });
 }
 
 }  // extern "C"

@@ -1,15 +1,20 @@
-// rt_frame.h -- internal: how a pass over the context's scene (the render in
-// rt_api.cpp, the first-hit feature pass in rt_aov.hip / librtow_aov.so), or a
-// pass that only shares the context's ordering (the denoiser in
-// rt_denoise.hip / librtow_denoise.so), starts and ends on a stream, and the
-// host helpers the three share (hip_fail / RT_HIP, rt_pass_scope,
-// rt_device_buf, rt_staging).  Not installed; rt_context stays opaque outside
-// rt_api.cpp, so the other libraries get what they need through rt_frame_setup.
+// rt_frame.h -- internal: how a pass of a context starts and ends on a stream,
+// and the host helpers its passes share.  A pass over the context's scene (the
+// render in rt_api.cpp, the first-hit feature pass in rt_aov.hip /
+// librtow_aov.so) begins with rt_internal_frame_begin; an image-space pass
+// that only shares the context's ordering (the denoiser in rt_denoise.hip /
+// librtow_denoise.so, temporal accumulation in rt_temporal.hip /
+// librtow_temporal.so) with rt_internal_pass_begin.  The helpers: hip_fail /
+// RT_HIP, rt_pass_scope, rt_device_buf and rt_sync_pass, the one
+// host sequence of the synchronous rt_aov / rt_denoise / rt_temporal.  Not
+// installed; rt_context stays opaque outside rt_api.cpp, so the other
+// libraries get what they need through rt_frame_setup.
 #ifndef RTOW_RT_FRAME_H
 #define RTOW_RT_FRAME_H
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstring>
 #include <utility>
 
@@ -41,7 +46,7 @@ int rt_internal_frame_check(const rt_context *ctx, const rt_camera *cam, const r
 int rt_internal_frame_begin(rt_context *ctx, const rt_camera *cam, const rt_params *params, void *stream,
                             rt_frame_setup *out);
 
-// The same for a pass that reads no scene (librtow_denoise.so): hipSetDevice
+// The same for a pass that reads no scene (the image-space passes): hipSetDevice
 // and the wait on the context's previous pass; of *out only stream, ev0 and
 // ev1 are set, the rest is zero.  RT_ERR_INVALID for a NULL argument, no HIP
 // call before that.  Ends with rt_internal_frame_end like the others.
@@ -127,27 +132,60 @@ struct rt_device_buf {
   }
 };
 
-// A synchronous wrapper's device buffers: 256-byte aligned parts of one
-// allocation, freed on leaving the scope.  add() the parts, alloc(), then at().
-class rt_staging {
- public:
-  size_t add(size_t bytes) {
-    const size_t off = total_;
-    total_ += (bytes + 255) / 256 * 256;
-    return off;
-  }
-  hipError_t alloc() { return hipMalloc((void **)&d_, total_); }
-  template <class T>
-  T *at(size_t off) const {
-    return reinterpret_cast<T *>(d_ + off);
-  }
-  rt_staging() = default;
-  rt_staging(const rt_staging &) = delete;
-  ~rt_staging() { (void)hipFree(d_); }
-
- private:
-  char *d_ = nullptr;
-  size_t total_ = 0;
+// One part of a synchronous pass's staging.
+struct rt_sync_part {
+  size_t bytes;    // 0: the part is left out (its device address is null)
+  const void *up;  // the host array copied in before the launches; null: none
+  void *down;      // the host array copied out after them; null: none
 };
+
+// A synchronous pass on the context's own stream, from host arrays to host
+// arrays: one device allocation cut into the parts (256-byte aligned), the
+// uploads, enqueue(dev, fs) -- dev[k] the device address of part k; it
+// enqueues the launches on fs.stream and returns their status -- between the
+// context's timing events, the wait, the downloads and *kernel_ms (0 unless
+// all of it succeeded).  The caller validates the arguments first; the first
+// error wins.  Whatever was enqueued, ev_done is recorded behind it
+// (rt_pass_scope), and the stream is drained before the allocation is freed,
+// also after a failure: the copies and launches read it and the host arrays.
+// wait() runs after a successful enqueue, before that drain: rt_aov waits
+// launch by launch there.
+template <size_t N, class Enqueue, class Wait = int (*)()>
+int rt_sync_pass(rt_context *c, const rt_camera *cam, const rt_params *prm, const rt_sync_part (&parts)[N],
+                 double *kernel_ms, Enqueue enqueue, Wait wait = [] { return (int)RT_OK; }) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  size_t off[N], total = 0;
+  for (size_t k = 0; k < N; ++k) off[k] = total, total += (parts[k].bytes + 255) / 256 * 256;
+  rt_device_buf<char> stage;  // (freed on leaving, after the drain)
+  void *dev[N] = {};
+  rt_pass_scope ps(c, cam, prm, nullptr);  // (sets the device)
+  const rt_frame_setup &fs = ps.fs;
+  const auto run = [&]() -> int {
+    if (ps.status != RT_OK) return ps.status;
+    RT_HIP(stage.grow(total));
+    for (size_t k = 0; k < N; ++k) {
+      dev[k] = parts[k].bytes ? stage.p + off[k] : nullptr;
+      if (dev[k] && parts[k].up)
+        RT_HIP(hipMemcpyAsync(dev[k], parts[k].up, parts[k].bytes, hipMemcpyHostToDevice, fs.stream));
+    }
+    RT_HIP(hipEventRecord(fs.ev0, fs.stream));
+    const int r = enqueue(dev, fs);
+    if (r == RT_OK) RT_HIP(hipEventRecord(fs.ev1, fs.stream));
+    return r;
+  };
+  int r = ps.end(run());
+  if (r == RT_OK) r = wait();
+  if (fs.stream) {
+    const hipError_t es = hipStreamSynchronize(fs.stream);
+    if (r == RT_OK && es != hipSuccess) r = hip_fail(es);
+  }
+  if (r != RT_OK) return r;
+  float ms = 0.0f;
+  RT_HIP(hipEventElapsedTime(&ms, fs.ev0, fs.ev1));
+  for (size_t k = 0; k < N; ++k)
+    if (dev[k] && parts[k].down) RT_HIP(hipMemcpy(parts[k].down, dev[k], parts[k].bytes, hipMemcpyDeviceToHost));
+  if (kernel_ms) *kernel_ms = ms;
+  return RT_OK;
+}
 
 #endif  // RTOW_RT_FRAME_H

@@ -3,8 +3,8 @@
 // host code that turns an rt_camera into the view the kernel projects with,
 // and the pass's host half.
 //
-// temporal_kernel prepares this frame's guides from the rt_aov sums (as
-// rt_denoise.hip's prepare_kernel does), projects the pixel's mean first-hit
+// temporal_kernel prepares this frame's guides from the rt_aov sums
+// (csrc/rt_post.h, shared with rt_denoise.hip), projects the pixel's mean first-hit
 // position through the previous frame's view, gathers the up to four history
 // taps around that point that lie on the same surface, blends them with the
 // new colour and writes the next frame's history and the caller's sums: one
@@ -27,17 +27,10 @@
 
 #include "rt_temporal.h"
 #include "rt_frame.h"
+#include "rt_post.h"
 
 namespace rtk {
 
-#define RT_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ RT_GLOBAL T *as_global(T *p) {
-  return (RT_GLOBAL T *)p;
-}
-
-constexpr int kTpTile = 16;  // 16 x 16 pixels per block: a wave is 16 x 4, its rows 256-byte runs of a plane
-constexpr int kTpMaxDim = 32768;
 constexpr int kTpDefaultMaxLen = 2, kTpMaxMaxLen = 1024;
 constexpr float kTpDefaultPlaneTol = 0.0003f, kTpDefaultNormalCos = 0.9f;
 
@@ -59,10 +52,6 @@ struct tp_params {
   f4 *hist_out;
 };
 
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-  return (ax * bx + ay * by) + az * bz;
-}
-
 // One lane per pixel.  The four taps are unrolled; a tap outside the frame, on
 // sky or on another surface is skipped per lane (its loads are predicated, so
 // no lane reads outside the planes).  Neighbouring lanes reproject to
@@ -70,9 +59,8 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 // taps fall in a few 256-byte runs of each plane and overlap in the vector
 // cache.
 __global__ __launch_bounds__(256) void temporal_kernel(const tp_params a) {
-  const int x = (int)blockIdx.x * kTpTile + (int)(threadIdx.x & (kTpTile - 1));
-  const int y = (int)blockIdx.y * kTpTile + (int)(threadIdx.x / kTpTile);
-  if (x >= a.width || y >= a.height) return;
+  int x, y;
+  if (!post_pixel(a.width, a.height, x, y)) return;
   const size_t npx = (size_t)a.width * (size_t)a.height;
   const size_t o = (size_t)y * (size_t)a.width + (size_t)x;
   // 1. prepare
@@ -80,33 +68,24 @@ __global__ __launch_bounds__(256) void temporal_kernel(const tp_params a) {
   const RT_GLOBAL float *g_p = as_global(a.position) + 3 * o;
   const RT_GLOBAL float *g_n = as_global(a.normal) + 3 * o;
   const uint32_t h = as_global(a.hits)[o];
-  const bool sky = h == 0;
-  const float hf = (float)h;
   const float cr = g_c[0] / a.spp_f, cg = g_c[1] / a.spp_f, cb = g_c[2] / a.spp_f;
-  const float ux = g_n[0] / hf, uy = g_n[1] / hf, uz = g_n[2] / hf;
-  const float nn = dot3(ux, uy, uz, ux, uy, uz);
-  const float nl = __builtin_sqrtf(nn);
-  const bool unit = !sky && nn > 0.0f;
-  const float nx = unit ? ux / nl : 0.0f;
-  const float ny = unit ? uy / nl : 0.0f;
-  const float nz = unit ? uz / nl : 0.0f;
-  const float Px = sky ? 0.0f : g_p[0] / hf;
-  const float Py = sky ? 0.0f : g_p[1] / hf;
-  const float Pz = sky ? 0.0f : g_p[2] / hf;
+  const post_guide g = post_prepare(h, g_p, g_n);
+  const bool sky = g.sky;
+  const float nx = g.nx, ny = g.ny, nz = g.nz, Px = g.px, Py = g.py, Pz = g.pz;
   // 2. no history
   float mr = cr, mg = cg, mb = cb, len = 1.0f;
   if (a.hist_in && !sky) {
     // 3. reproject
     const float qx = Px - a.prev.eye[0], qy = Py - a.prev.eye[1], qz = Pz - a.prev.eye[2];
-    const float w = dot3(a.prev.pw[0], a.prev.pw[1], a.prev.pw[2], qx, qy, qz);
-    const float fxp = dot3(a.prev.px[0], a.prev.px[1], a.prev.px[2], qx, qy, qz) / w - a.prev.x0;
-    const float fyp = dot3(a.prev.py[0], a.prev.py[1], a.prev.py[2], qx, qy, qz) / w - a.prev.y0;
+    const float w = dot3_unfused(a.prev.pw[0], a.prev.pw[1], a.prev.pw[2], qx, qy, qz);
+    const float fxp = dot3_unfused(a.prev.px[0], a.prev.px[1], a.prev.px[2], qx, qy, qz) / w - a.prev.x0;
+    const float fyp = dot3_unfused(a.prev.py[0], a.prev.py[1], a.prev.py[2], qx, qy, qz) / w - a.prev.y0;
     const bool ok = w > 0.0f && fxp > -1.0f && fxp < a.width_f && fyp > -1.0f && fyp < a.height_f;
     if (ok) {
       const float xf = __builtin_floorf(fxp), yf = __builtin_floorf(fyp);
       const float fx = fxp - xf, fy = fyp - yf;
       const int xi = (int)xf, yi = (int)yf;  // -1 .. W-1, -1 .. H-1
-      const float d2 = dot3(qx, qy, qz, qx, qy, qz);
+      const float d2 = dot3_unfused(qx, qy, qz, qx, qy, qz);
       const float lim = a.pt2 * d2;
       const RT_GLOBAL f4 *__restrict__ h0 = as_global(a.hist_in);
       const RT_GLOBAL f4 *__restrict__ h1 = h0 + npx;
@@ -123,9 +102,9 @@ __global__ __launch_bounds__(256) void temporal_kernel(const tp_params a) {
           const f4 pt = h1[t];
           if (pt.w != 0.0f) continue;
           const f4 nt = h2[t];
-          const float e = dot3(nx, ny, nz, pt.x - Px, pt.y - Py, pt.z - Pz);
+          const float e = dot3_unfused(nx, ny, nz, pt.x - Px, pt.y - Py, pt.z - Pz);
           if (a.plane_test && !(e * e <= lim)) continue;
-          const float g = dot3(nx, ny, nz, nt.x, nt.y, nt.z);
+          const float g = dot3_unfused(nx, ny, nz, nt.x, nt.y, nt.z);
           if (a.normal_test && !(g >= a.normal_cos)) continue;
           const f4 ct = h0[t];
           const float b = (dx ? fx : 1.0f - fx) * (dy ? fy : 1.0f - fy);
@@ -184,8 +163,6 @@ struct tp_options {
   float plane_tol, normal_cos;
 };
 
-bool size_ok(int w, int h) { return w >= 1 && h >= 1 && w <= rtk::kTpMaxDim && h <= rtk::kTpMaxDim; }
-
 bool overlap(const void *p, size_t np, const void *q, size_t nq) {
   const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
   return p && q && a < b + nq && b < a + np;
@@ -193,7 +170,7 @@ bool overlap(const void *p, size_t np, const void *q, size_t nq) {
 
 // false: an argument is NULL, out of range or NaN, or the buffers overlap
 bool resolve(const rt_temporal_desc *d, tp_options &o) {
-  if (!size_ok(d->width, d->height)) return false;
+  if (!rtk::post_size_ok(d->width, d->height)) return false;
   if (d->spp < 1 || d->reserved[0] != 0 || d->reserved[1] != 0) return false;
   if (!d->cur || !d->hits || !d->position || !d->normal || !d->history_out) return false;
   o.max_len = d->max_len == 0 ? rtk::kTpDefaultMaxLen : d->max_len;
@@ -233,9 +210,7 @@ int enqueue(const rt_temporal_desc *d, const tp_options &o, hipStream_t st) {
   a.out = d->out;
   a.hist_in = static_cast<const rtk::f4 *>(d->history_in);
   a.hist_out = static_cast<rtk::f4 *>(d->history_out);
-  const dim3 grid((unsigned)((d->width + rtk::kTpTile - 1) / rtk::kTpTile),
-                  (unsigned)((d->height + rtk::kTpTile - 1) / rtk::kTpTile));
-  rtk::temporal_kernel<<<grid, 256, 0, st>>>(a);
+  rtk::temporal_kernel<<<rtk::post_grid(d->width, d->height), 256, 0, st>>>(a);
   RT_HIP(hipGetLastError());
   return RT_OK;
 }
@@ -261,12 +236,12 @@ extern "C" {
 int rt_temporal_version(void) { return RT_TEMPORAL_VERSION; }
 
 size_t rt_temporal_history_bytes(int width, int height) {
-  if (!size_ok(width, height)) return 0;
+  if (!rtk::post_size_ok(width, height)) return 0;
   return 48 * (size_t)width * (size_t)height;
 }
 
 int rt_temporal_view_from_camera(const rt_camera *cam, int width, int height, rt_temporal_view *out) {
-  if (!cam || !out || !size_ok(width, height)) return RT_ERR_INVALID;
+  if (!cam || !out || !rtk::post_size_ok(width, height)) return RT_ERR_INVALID;
   if (cam->model != RT_CAMERA_CPU && cam->model != RT_CAMERA_GPU) return RT_ERR_INVALID;
   if (cam->model == RT_CAMERA_CPU && (width < 2 || height < 2)) return RT_ERR_INVALID;
   const d3 eye = of(cam->eye), hz = of(cam->horiz), vt = of(cam->vert);
@@ -311,49 +286,23 @@ int rt_temporal_async(rt_context *c, const rt_temporal_desc *d, void *stream) {
 int rt_temporal(rt_context *c, const rt_temporal_desc *host, double *kernel_ms) {
   tp_options o;
   if (!c || !host || !resolve(host, o)) return RT_ERR_INVALID;
-  if (kernel_ms) *kernel_ms = 0.0;
   const size_t npx = (size_t)host->width * (size_t)host->height;
-  // one allocation: cur / out (blended in place), hits, position, normal,
-  // history in (when there is one), history out; every part 256-byte aligned
-  const void *hp[5] = {host->cur, host->hits, host->position, host->normal, host->history_in};
-  const size_t bytes[6] = {12 * npx, 4 * npx, 12 * npx, 12 * npx, host->history_in ? 48 * npx : 0, 48 * npx};
-  rt_staging stage;
-  size_t off[6];
-  for (int k = 0; k < 6; ++k) off[k] = stage.add(bytes[k]);
-  rt_pass_scope ps(c, nullptr, nullptr, nullptr);  // (sets the device)
-  const rt_frame_setup &fs = ps.fs;
-  const auto run = [&]() -> int {
-    if (ps.status != RT_OK) return ps.status;
-    RT_HIP(stage.alloc());
-    for (int k = 0; k < 5; ++k)
-      if (bytes[k])
-        RT_HIP(hipMemcpyAsync(stage.at<char>(off[k]), hp[k], bytes[k], hipMemcpyHostToDevice, fs.stream));
-    RT_HIP(hipEventRecord(fs.ev0, fs.stream));
-    rt_temporal_desc dev = *host;
-    dev.cur = stage.at<float>(off[0]);
-    dev.out = host->out ? stage.at<float>(off[0]) : nullptr;
-    dev.hits = stage.at<uint32_t>(off[1]);
-    dev.position = stage.at<float>(off[2]);
-    dev.normal = stage.at<float>(off[3]);
-    dev.history_in = host->history_in ? stage.at<char>(off[4]) : nullptr;
-    dev.history_out = stage.at<char>(off[5]);
-    const int r = enqueue(&dev, o, fs.stream);
-    if (r == RT_OK) RT_HIP(hipEventRecord(fs.ev1, fs.stream));
-    return r;
-  };
-  int r = ps.end(run());
-  if (fs.stream) {
-    // whatever was enqueued reads the host arrays and the allocation: wait
-    const hipError_t es = hipStreamSynchronize(fs.stream);
-    if (r == RT_OK && es != hipSuccess) r = hip_fail(es);
-  }
-  if (r != RT_OK) return r;
-  float ms = 0.0f;
-  RT_HIP(hipEventElapsedTime(&ms, fs.ev0, fs.ev1));
-  RT_HIP(hipMemcpy(host->history_out, stage.at<char>(off[5]), bytes[5], hipMemcpyDeviceToHost));
-  if (host->out) RT_HIP(hipMemcpy(host->out, stage.at<char>(off[0]), bytes[0], hipMemcpyDeviceToHost));
-  if (kernel_ms) *kernel_ms = ms;
-  return RT_OK;
+  // cur / out (blended in place), hits, position, normal, history in (when there is one), history out
+  const rt_sync_part parts[6] = {{12 * npx, host->cur, host->out}, {4 * npx, host->hits, nullptr},
+                                 {12 * npx, host->position, nullptr}, {12 * npx, host->normal, nullptr},
+                                 {host->history_in ? 48 * npx : 0, host->history_in, nullptr},
+                                 {48 * npx, nullptr, host->history_out}};
+  return rt_sync_pass(c, nullptr, nullptr, parts, kernel_ms, [&](void *const *dev, const rt_frame_setup &fs) {
+    rt_temporal_desc d = *host;
+    d.cur = static_cast<float *>(dev[0]);
+    d.out = host->out ? static_cast<float *>(dev[0]) : nullptr;
+    d.hits = static_cast<uint32_t *>(dev[1]);
+    d.position = static_cast<float *>(dev[2]);
+    d.normal = static_cast<float *>(dev[3]);
+    d.history_in = dev[4];
+    d.history_out = dev[5];
+    return enqueue(&d, o, fs.stream);
+  });
 }
 
 }  // extern "C"

@@ -140,28 +140,47 @@ _denoise_lib = None
 _temporal_lib = None
 
 
+def _missing(path):
+    return RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; "
+                        "g.build()'` (or make -C ray-tracing-in-one-weekend_amd)")
+
+
+def _reject_unknown(names, known, what):
+    unknown = [k for k in names if k not in known]
+    if unknown:
+        raise ValueError(f"unknown {what} {unknown}")
+
+
+def _load_pass(path, version_fn, version, protos):
+    """Load a pass's library (raises if it has not been built): librtow.so
+    loads first, since the pass runs on its contexts; protos maps function
+    names to (restype or None = int, argtypes); version_fn() must give
+    `version`, the constant the header names version_fn.upper()."""
+    lib()
+    if not os.path.exists(path):
+        raise _missing(path)
+    L = ctypes.CDLL(path)
+    for name, (restype, argtypes) in protos.items():
+        getattr(L, name).argtypes = argtypes
+        if restype is not None:
+            getattr(L, name).restype = restype
+    got = getattr(L, version_fn)()
+    if got != version:
+        raise RuntimeError(f"{path}: {version_fn.upper()} {got}, expected {version}")
+    return L
+
+
 def temporal_lib():
     """Load librtow_temporal.so, temporal accumulation with reprojection
-    (raises if it has not been built).  librtow.so loads first: the pass runs
-    on its contexts."""
+    (raises if it has not been built)."""
     global _temporal_lib
     if _temporal_lib is None:
-        lib()
-        if not os.path.exists(TEMPORAL_LIB_PATH):
-            raise RuntimeError(f"{TEMPORAL_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or make -C ray-tracing-in-one-weekend_amd)")
-        L = ctypes.CDLL(TEMPORAL_LIB_PATH)
-        L.rt_temporal_version.restype = ctypes.c_int
-        L.rt_temporal_history_bytes.restype = ctypes.c_size_t
-        L.rt_temporal_history_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.rt_temporal_view_from_camera.argtypes = [ctypes.POINTER(Camera), ctypes.c_int, ctypes.c_int,
-                                                   ctypes.POINTER(TemporalView)]
-        L.rt_temporal_async.argtypes = [ctypes.c_void_p, ctypes.POINTER(TemporalDesc), ctypes.c_void_p]
-        L.rt_temporal.argtypes = [ctypes.c_void_p, ctypes.POINTER(TemporalDesc), ctypes.POINTER(ctypes.c_double)]
-        if L.rt_temporal_version() != TEMPORAL_VERSION:
-            raise RuntimeError(f"{TEMPORAL_LIB_PATH}: RT_TEMPORAL_VERSION {L.rt_temporal_version()}, "
-                               f"expected {TEMPORAL_VERSION}")
-        _temporal_lib = L
+        _temporal_lib = _load_pass(TEMPORAL_LIB_PATH, "rt_temporal_version", TEMPORAL_VERSION, {
+            "rt_temporal_history_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+            "rt_temporal_view_from_camera": (None, [ctypes.POINTER(Camera), ctypes.c_int, ctypes.c_int,
+                                                    ctypes.POINTER(TemporalView)]),
+            "rt_temporal_async": (None, [ctypes.c_void_p, ctypes.POINTER(TemporalDesc), ctypes.c_void_p]),
+            "rt_temporal": (None, [ctypes.c_void_p, ctypes.POINTER(TemporalDesc), ctypes.POINTER(ctypes.c_double)])})
     return _temporal_lib
 
 
@@ -189,9 +208,7 @@ def temporal_desc(width, height, spp, prev_view=None, **options):
     or None take their defaults; a value means itself: plane_tol=inf and
     normal_cos=-1 switch their tests off.  The struct reads 0 as "default", so
     max_len=0, plane_tol=0 and normal_cos=0 cannot be asked for."""
-    unknown = [k for k in options if k not in TEMPORAL_DEFAULTS]
-    if unknown:
-        raise ValueError(f"unknown temporal options {unknown}")
+    _reject_unknown(options, TEMPORAL_DEFAULTS, "temporal options")
     opt = {k: v for k, v in options.items() if v is not None}
     zero = [k for k, v in opt.items() if v == 0]
     if zero:
@@ -207,24 +224,14 @@ def temporal_desc(width, height, spp, prev_view=None, **options):
 
 def denoise_lib():
     """Load librtow_denoise.so, the guided a-trous filter (raises if it has
-    not been built).  librtow.so loads first: the filter runs on its contexts."""
+    not been built)."""
     global _denoise_lib
     if _denoise_lib is None:
-        lib()
-        if not os.path.exists(DENOISE_LIB_PATH):
-            raise RuntimeError(f"{DENOISE_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or make -C ray-tracing-in-one-weekend_amd)")
-        L = ctypes.CDLL(DENOISE_LIB_PATH)
-        L.rt_denoise_version.restype = ctypes.c_int
-        L.rt_denoise_scratch_bytes.restype = ctypes.c_size_t
-        L.rt_denoise_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.rt_denoise_async.argtypes = [ctypes.c_void_p, ctypes.POINTER(DenoiseDesc), ctypes.c_void_p,
-                                       ctypes.c_void_p]
-        L.rt_denoise.argtypes = [ctypes.c_void_p, ctypes.POINTER(DenoiseDesc), ctypes.POINTER(ctypes.c_double)]
-        if L.rt_denoise_version() != DENOISE_VERSION:
-            raise RuntimeError(f"{DENOISE_LIB_PATH}: RT_DENOISE_VERSION {L.rt_denoise_version()}, "
-                               f"expected {DENOISE_VERSION}")
-        _denoise_lib = L
+        _denoise_lib = _load_pass(DENOISE_LIB_PATH, "rt_denoise_version", DENOISE_VERSION, {
+            "rt_denoise_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+            "rt_denoise_async": (None, [ctypes.c_void_p, ctypes.POINTER(DenoiseDesc), ctypes.c_void_p,
+                                        ctypes.c_void_p]),
+            "rt_denoise": (None, [ctypes.c_void_p, ctypes.POINTER(DenoiseDesc), ctypes.POINTER(ctypes.c_double)])})
     return _denoise_lib
 
 
@@ -233,9 +240,7 @@ def denoise_desc(width, height, spp, **options):
     None take their defaults; here a value means itself, so normal_power=0 is
     "no squaring" and sigma_color=0 / sigma_plane=inf switch their terms off
     (the struct's own 0 = default and -1 = off encoding stays inside)."""
-    unknown = [k for k in options if k not in DENOISE_DEFAULTS]
-    if unknown:
-        raise ValueError(f"unknown denoise options {unknown}")
+    _reject_unknown(options, DENOISE_DEFAULTS, "denoise options")
     opt = {k: v for k, v in options.items() if v is not None}
     if opt.get("iterations", 1) == 0 or opt.get("sigma_plane", 1) == 0:
         raise ValueError("iterations and sigma_plane must be positive")
@@ -249,22 +254,14 @@ def denoise_desc(width, height, spp, **options):
 
 def aov_lib():
     """Load librtow_aov.so, the first-hit feature pass (raises if it has not
-    been built).  librtow.so loads first: the pass runs on its contexts."""
+    been built)."""
     global _aov_lib
     if _aov_lib is None:
-        lib()
-        if not os.path.exists(AOV_LIB_PATH):
-            raise RuntimeError(f"{AOV_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or make -C ray-tracing-in-one-weekend_amd)")
-        L = ctypes.CDLL(AOV_LIB_PATH)
-        L.rt_aov_version.restype = ctypes.c_int
-        L.rt_aov_async.argtypes = [ctypes.c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Params),
-                                   ctypes.POINTER(AovBuffers), ctypes.c_void_p]
-        L.rt_aov.argtypes = [ctypes.c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Params),
-                             ctypes.POINTER(AovBuffers), ctypes.POINTER(ctypes.c_double)]
-        if L.rt_aov_version() != AOV_VERSION:
-            raise RuntimeError(f"{AOV_LIB_PATH}: RT_AOV_VERSION {L.rt_aov_version()}, expected {AOV_VERSION}")
-        _aov_lib = L
+        _aov_lib = _load_pass(AOV_LIB_PATH, "rt_aov_version", AOV_VERSION, {
+            "rt_aov_async": (None, [ctypes.c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Params),
+                                    ctypes.POINTER(AovBuffers), ctypes.c_void_p]),
+            "rt_aov": (None, [ctypes.c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Params),
+                              ctypes.POINTER(AovBuffers), ctypes.POINTER(ctypes.c_double)])})
     return _aov_lib
 
 
@@ -273,8 +270,7 @@ def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or make -C ray-tracing-in-one-weekend_amd)")
+            raise _missing(LIB_PATH)
         # torch's bundled HIP runtime has the same soname as the system one
         # librtow links (libamdhip64.so.7): whichever loads first serves the
         # process, and torch cannot enumerate devices through the system's.
@@ -368,6 +364,15 @@ def device_code_sha16(path=None):
 
 def _ptr(a, t):
     return a.ctypes.data_as(t)
+
+
+def _frame_array(name, a, dtype, d, lead=(), tail=(3,)):
+    """a as a C-contiguous array of dtype, checked against the shape
+    lead + (height, width) + tail of the desc d's frame."""
+    a = np.ascontiguousarray(a, dtype)
+    if a.shape != lead + (d.height, d.width) + tail:
+        raise ValueError(f"{name}: shape {a.shape} does not match the {d.width} x {d.height} frame")
+    return a
 
 
 @dataclass
@@ -553,9 +558,7 @@ class Context:
         (local_rows, W) or (local_rows, W, 3) for the names in `which`, holding
         unnormalised sums over each pixel's hit samples (divide by "hits"), plus
         "kernel_ms"."""
-        unknown = [w for w in which if w not in [f[0] for f in AOV_FIELDS]]
-        if unknown:
-            raise ValueError(f"unknown feature buffers {unknown}")
+        _reject_unknown(which, [f[0] for f in AOV_FIELDS], "feature buffers")
         out, bufs = {}, AovBuffers()
         for name, dt, ch in AOV_FIELDS:
             if name in which:
@@ -572,9 +575,7 @@ class Context:
         """Enqueue the first-hit pass (rt_aov_async) into raw device pointers
         (e.g. torch tensor.data_ptr()): dev_ptrs maps names of AOV_FIELDS to
         device pointers; names left out are not computed."""
-        unknown = [w for w in dev_ptrs if w not in [f[0] for f in AOV_FIELDS]]
-        if unknown:
-            raise ValueError(f"unknown feature buffers {unknown}")
+        _reject_unknown(dev_ptrs, [f[0] for f in AOV_FIELDS], "feature buffers")
         bufs = AovBuffers()
         for name, ptr in dev_ptrs.items():
             setattr(bufs, name, ptr)
@@ -592,13 +593,11 @@ class Context:
         missing = [k for k in DENOISE_INPUTS[1:] if k not in aov]
         if missing:
             raise ValueError(f"feature buffers {missing} are missing")
-        keep = {"beauty": np.ascontiguousarray(beauty, np.float32),
-                "hits": np.ascontiguousarray(aov["hits"], np.uint32)}
+        keep = {"beauty": _frame_array("beauty", beauty, np.float32, d),
+                "hits": _frame_array("hits", aov["hits"], np.uint32, d, tail=())}
         for k in DENOISE_INPUTS[2:]:
-            keep[k] = np.ascontiguousarray(aov[k], np.float32)
+            keep[k] = _frame_array(k, aov[k], np.float32, d)
         for k, a in keep.items():
-            if a.shape != (d.height, d.width) + ((3,) if k != "hits" else ()):
-                raise ValueError(f"{k}: shape {a.shape} does not match the {d.width} x {d.height} frame")
             setattr(d, k, a.ctypes.data)
         out = np.zeros((d.height, d.width, 3), np.float32)
         d.out = out.ctypes.data
@@ -612,9 +611,7 @@ class Context:
         torch tensor.data_ptr()): dev_ptrs maps DENOISE_INPUTS and "out" to
         device pointers ("out" may be the beauty buffer), scratch_ptr is
         denoise_lib().rt_denoise_scratch_bytes(width, height) bytes."""
-        unknown = [k for k in dev_ptrs if k not in DENOISE_INPUTS + ("out",)]
-        if unknown:
-            raise ValueError(f"unknown denoise buffers {unknown}")
+        _reject_unknown(dev_ptrs, DENOISE_INPUTS + ("out",), "denoise buffers")
         d = denoise_desc(width, height, spp, **options)
         for name, ptr in dev_ptrs.items():
             setattr(d, name, ptr)
@@ -637,15 +634,13 @@ class Context:
         missing = [k for k in TEMPORAL_BUFFERS[1:4] if k not in aov]
         if missing:
             raise ValueError(f"feature buffers {missing} are missing")
-        keep = {"cur": np.ascontiguousarray(cur, np.float32), "hits": np.ascontiguousarray(aov["hits"], np.uint32)}
+        keep = {"cur": _frame_array("cur", cur, np.float32, d),
+                "hits": _frame_array("hits", aov["hits"], np.uint32, d, tail=())}
         for k in TEMPORAL_BUFFERS[2:4]:
-            keep[k] = np.ascontiguousarray(aov[k], np.float32)
-        shapes = {"hits": (d.height, d.width), "history_in": (3, d.height, d.width, 4)}
+            keep[k] = _frame_array(k, aov[k], np.float32, d)
         if history is not None:
-            keep["history_in"] = np.ascontiguousarray(history, np.float32)
+            keep["history_in"] = _frame_array("history_in", history, np.float32, d, lead=(3,), tail=(4,))
         for k, a in keep.items():
-            if a.shape != shapes.get(k, (d.height, d.width, 3)):
-                raise ValueError(f"{k}: shape {a.shape} does not match the {d.width} x {d.height} frame")
             setattr(d, k, a.ctypes.data)
         out = np.zeros((d.height, d.width, 3), np.float32)
         history_out = np.zeros((3, d.height, d.width, 4), np.float32)
@@ -663,9 +658,7 @@ class Context:
         temporal_lib().rt_temporal_history_bytes(width, height) bytes each and
         must not overlap); prev_view: the view history_in was made with (None
         without one)."""
-        unknown = [k for k in dev_ptrs if k not in TEMPORAL_BUFFERS]
-        if unknown:
-            raise ValueError(f"unknown temporal buffers {unknown}")
+        _reject_unknown(dev_ptrs, TEMPORAL_BUFFERS, "temporal buffers")
         d = temporal_desc(width, height, spp, prev_view, **options)
         for name, ptr in dev_ptrs.items():
             setattr(d, name, ptr)

@@ -9,13 +9,10 @@ normal_power 0 = no squaring, sigma_plane inf = term off, sigma_color 0 = term
 off."""
 import numpy as np
 
-F = np.float32
+from post_ref import F, _dot, guides
+
 K = (F(1 / 16), F(4 / 16), F(6 / 16), F(4 / 16), F(1 / 16))
 DEFAULTS = dict(iterations=5, normal_power=6, sigma_plane=0.5, sigma_color=0.15)
-
-
-def _dot(a, b):
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
 
 
 def demod(albedo, hits, spp):
@@ -30,16 +27,9 @@ def prepare(beauty, hits, position, normal, albedo, spp):
     sky mask, and the albedo m the colour was divided by."""
     beauty, position, normal, albedo = (np.asarray(x, F) for x in (beauty, position, normal, albedo))
     hits = np.asarray(hits, np.uint32)
-    sky = hits == 0
     m = demod(albedo, hits, spp)
     u = (beauty / F(spp)) / m
-    hf = hits.astype(F)[..., None]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        n = normal / hf
-        nn = _dot(n, n)
-        unit = ~sky & (nn > 0)
-        n = np.where(unit[..., None], n / np.sqrt(nn)[..., None], F(0)).astype(F)
-        P = np.where(sky[..., None], F(0), position / hf).astype(F)
+    n, P, sky = guides(normal, position, hits)
     return u.astype(F), n, P, sky, m
 
 

@@ -11,16 +11,13 @@ from collections import namedtuple
 
 import numpy as np
 
-F = np.float32
+from post_ref import F, _dot, guides
+
 DEFAULTS = dict(max_len=2, plane_tol=0.0003, normal_cos=0.9)
 
 # rt_temporal_view; anything with these attributes (rtow.TemporalView too) is a view here
 View = namedtuple("View", "eye px py pw x0 y0")
 IDENTITY = View(eye=(0.0, 0.0, 0.0), px=(1.0, 0.0, 0.0), py=(0.0, 1.0, 0.0), pw=(0.0, 0.0, 1.0), x0=0.0, y0=0.0)
-
-
-def _dot(a, b):
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
 
 
 def _v3(v):
@@ -42,15 +39,8 @@ def prepare(cur, hits, position, normal, spp):
     """-> (c, n, P, sky): mean colour, unit normal, mean position, sky mask."""
     cur, position, normal = (np.asarray(a, F) for a in (cur, position, normal))
     hits = np.asarray(hits, np.uint32)
-    sky = hits == 0
     c = cur / F(spp)
-    hf = hits.astype(F)[..., None]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        n = normal / hf
-        nn = _dot(n, n)
-        unit = ~sky & (nn > 0)
-        n = np.where(unit[..., None], n / np.sqrt(nn)[..., None], F(0)).astype(F)
-        P = np.where(sky[..., None], F(0), position / hf).astype(F)
+    n, P, sky = guides(normal, position, hits)
     return c.astype(F), n, P, sky
 
 

@@ -175,6 +175,58 @@ def test_temporal_async_in_place_and_without_out(rtow, gpu_ctx):
     assert cur.tobytes() == want_out.tobytes()
 
 
+def test_async_chain_of_all_passes_equals_the_synchronous_chain(rtow, gpu_ctx):
+    """render -> aov -> denoise -> temporal of two consecutive orbit frames of
+    the five-sphere scene (67x37, 4 spp), enqueued on one caller stream into
+    torch device buffers, the second frame's history the first one's: the bytes
+    of the same chain through the synchronous Context.aov / denoise / temporal,
+    whose staging uploads and downloads every buffer in between."""
+    import torch
+    w, h = 67, 37
+    gpu_ctx.upload(rtow.five_scene())
+    cams = orbit_cameras(rtow, "five", w, h, 2, 2.0)
+    frames = [(cam, rtow.make_params(w, h, SPP, seed=1 + i, flags=rtow.RT_FLAG_ACCEL_BVH), rtow.temporal_view(cam, w, h))
+              for i, cam in enumerate(cams)]
+    want = []
+    hist = prev = None
+    for cam, p, view in frames:
+        g = gpu_ctx.aov(cam, p)
+        den = gpu_ctx.denoise(gpu_ctx.render(cam, p)[0], g, SPP)
+        out, hist = gpu_ctx.temporal(den, g, SPP, prev, hist)
+        want.append((den, out, hist))
+        prev = view
+    dev = torch.device("cuda:0")
+
+    def buf(*shape, dtype=torch.float32):
+        return torch.full(shape, 7, dtype=dtype, device=dev)
+    t = dict(beauty=buf(h, w, 3), hits=buf(h, w, dtype=torch.int32), position=buf(h, w, 3), normal=buf(h, w, 3),
+             albedo=buf(h, w, 3), den=buf(h, w, 3), out=buf(h, w, 3))
+    hists = [buf(3, h, w, 4), buf(3, h, w, 4)]
+    scratch = torch.empty(rtow.denoise_lib().rt_denoise_scratch_bytes(w, h), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.Stream(device=dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    ptr = {k: v.data_ptr() for k, v in t.items()}
+    prev = None
+    for i, (cam, p, view) in enumerate(frames):
+        gpu_ctx.render_async(cam, p, ptr["beauty"], stream.cuda_stream)
+        gpu_ctx.aov_async(cam, p, {k: ptr[k] for k in ("hits", "position", "normal", "albedo")},
+                          stream=stream.cuda_stream)
+        gpu_ctx.denoise_async({**{k: ptr[k] for k in rtow.DENOISE_INPUTS}, "out": ptr["den"]}, w, h, SPP,
+                              scratch.data_ptr(), stream=stream.cuda_stream)
+        gpu_ctx.temporal_async({"cur": ptr["den"], "hits": ptr["hits"], "position": ptr["position"],
+                                "normal": ptr["normal"], "history_in": hists[1 - i].data_ptr() if i else None,
+                                "history_out": hists[i].data_ptr(), "out": ptr["out"]},
+                               w, h, SPP, prev, stream=stream.cuda_stream)
+        stream.synchronize()
+        den, out, hist = want[i]
+        assert t["den"].cpu().numpy().tobytes() == den.tobytes(), i
+        assert t["out"].cpu().numpy().tobytes() == out.tobytes(), i
+        assert hists[i].cpu().numpy().tobytes() == hist.tobytes(), i
+        prev = view
+    geo = want[1][2][1, ..., 3] == 0
+    assert (want[1][2][0, ..., 3][geo] > 1).mean() > 0.5  # the second frame did use the first one's history
+
+
 def test_temporal_between_renders_leaves_them_alone(rtow, gpu_ctx):
     """The pass shares the context's serialisation and nothing else: a render
     before it and a render after it give the same bytes, and it needs no scene
