@@ -28,6 +28,8 @@ AOV_LIB_PATH = os.path.join(HERE, "librtow_aov.so")
 DENOISE_LIB_PATH = os.path.join(HERE, "librtow_denoise.so")
 # temporal accumulation with camera reprojection (include/rt_temporal.h): a fourth
 TEMPORAL_LIB_PATH = os.path.join(HERE, "librtow_temporal.so")
+# the clamped temporal resolve with centre reprojection (include/rt_resolve.h): a fifth
+RESOLVE_LIB_PATH = os.path.join(HERE, "librtow_resolve.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
@@ -56,6 +58,11 @@ TEMPORAL_VERSION = 1  # include/rt_temporal.h RT_TEMPORAL_VERSION
 # rt_temporal_desc's pointers in order (history_in and out may be NULL), and its options with their defaults
 TEMPORAL_BUFFERS = ("cur", "hits", "position", "normal", "history_in", "history_out", "out")
 TEMPORAL_DEFAULTS = {"max_len": 2, "plane_tol": 0.0003, "normal_cos": 0.9}
+RESOLVE_VERSION = 1  # include/rt_resolve.h RT_RESOLVE_VERSION
+# rt_resolve_desc's pointers in order (history_in and out may be NULL), its options with their defaults, its flags
+RESOLVE_BUFFERS = ("cur", "hits", "depth", "normal", "history_in", "history_out", "out")
+RESOLVE_DEFAULTS = {"max_len": 2, "plane_tol": 0.003, "normal_cos": 0.9, "gamma": 1.0}
+RESOLVE_KEEP_PARTIAL = 1  # RT_RESOLVE_KEEP_PARTIAL
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
 RT_OPT_BVH_COLLAPSE, RT_OPT_BVH_SIDE, RT_OPT_LAUNCH_SAMPLES, RT_OPT_GRID_FIT = 4, 5, 6, 7
@@ -134,10 +141,28 @@ class TemporalDesc(ctypes.Structure):
                 [(name, ctypes.c_void_p) for name in TEMPORAL_BUFFERS])
 
 
+class ResolveRays(ctypes.Structure):
+    """rt_resolve_rays: the unnormalised centre ray of pixel (col, row) is
+    (d00 + col * du) + row * dv, from eye."""
+    _fields_ = [(name, ctypes.c_float * 3) for name in ("eye", "d00", "du", "dv")]
+
+
+class ResolveDesc(ctypes.Structure):
+    """rt_resolve_desc: the frame, the options (0 = default), the flags, the
+    previous frame's view, this frame's centre rays and device
+    (rt_resolve_async) or host (rt_resolve) pointers."""
+    _fields_ = ([(name, ctypes.c_int32) for name in ("width", "height", "spp", "max_len")] +
+                [("plane_tol", ctypes.c_float), ("normal_cos", ctypes.c_float), ("gamma", ctypes.c_float),
+                 ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("prev", TemporalView),
+                 ("now", ResolveRays)] +
+                [(name, ctypes.c_void_p) for name in RESOLVE_BUFFERS])
+
+
 _lib = None
 _aov_lib = None
 _denoise_lib = None
 _temporal_lib = None
+_resolve_lib = None
 
 
 def _missing(path):
@@ -219,6 +244,62 @@ def temporal_desc(width, height, spp, prev_view=None, **options):
     d.normal_cos = float(opt.get("normal_cos", 0.0))
     if prev_view is not None:
         d.prev = as_temporal_view(prev_view)
+    return d
+
+
+def resolve_lib():
+    """Load librtow_resolve.so, the clamped temporal resolve with centre
+    reprojection (raises if it has not been built)."""
+    global _resolve_lib
+    if _resolve_lib is None:
+        _resolve_lib = _load_pass(RESOLVE_LIB_PATH, "rt_resolve_version", RESOLVE_VERSION, {
+            "rt_resolve_rays_from_camera": (None, [ctypes.POINTER(Camera), ctypes.c_int, ctypes.c_int,
+                                                   ctypes.POINTER(ResolveRays)]),
+            "rt_resolve_async": (None, [ctypes.c_void_p, ctypes.POINTER(ResolveDesc), ctypes.c_void_p]),
+            "rt_resolve": (None, [ctypes.c_void_p, ctypes.POINTER(ResolveDesc), ctypes.POINTER(ctypes.c_double)])})
+    return _resolve_lib
+
+
+def resolve_rays(cam, width, height):
+    """The ResolveRays of a camera for a width x height frame
+    (rt_resolve_rays_from_camera): what THIS frame's pass gets as now_rays."""
+    r = ResolveRays()
+    check(resolve_lib().rt_resolve_rays_from_camera(ctypes.byref(cam), width, height, ctypes.byref(r)),
+          "rt_resolve_rays_from_camera")
+    return r
+
+
+def as_resolve_rays(rays):
+    """A ResolveRays from anything with eye, d00, du and dv (three numbers each)."""
+    if isinstance(rays, ResolveRays):
+        return rays
+    r = ResolveRays()
+    for name in ("eye", "d00", "du", "dv"):
+        setattr(r, name, (ctypes.c_float * 3)(*[float(x) for x in getattr(rays, name)]))
+    return r
+
+
+def resolve_desc(width, height, spp, prev_view=None, now_rays=None, flags=0, **options):
+    """A ResolveDesc without pointers.  Options (RESOLVE_DEFAULTS) left out or
+    None take their defaults; a value means itself: plane_tol=inf,
+    normal_cos=-1 and gamma=inf switch their steps off.  The struct reads 0 as
+    "default", so an option of 0 cannot be asked for.  flags:
+    RESOLVE_KEEP_PARTIAL or 0."""
+    _reject_unknown(options, RESOLVE_DEFAULTS, "resolve options")
+    opt = {k: v for k, v in options.items() if v is not None}
+    zero = [k for k, v in opt.items() if v == 0]
+    if zero:
+        raise ValueError(f"resolve options {zero} must not be 0 (the struct's 0 means the default)")
+    if now_rays is None:
+        raise ValueError("now_rays (resolve_rays of this frame's camera) is required")
+    d = ResolveDesc(width=width, height=height, spp=spp, flags=int(flags))
+    d.max_len = int(opt.get("max_len", 0))
+    d.plane_tol = float(opt.get("plane_tol", 0.0))
+    d.normal_cos = float(opt.get("normal_cos", 0.0))
+    d.gamma = float(opt.get("gamma", 0.0))
+    if prev_view is not None:
+        d.prev = as_temporal_view(prev_view)
+    d.now = as_resolve_rays(now_rays)
     return d
 
 
@@ -664,6 +745,53 @@ class Context:
             setattr(d, name, ptr)
         check(temporal_lib().rt_temporal_async(self._h, ctypes.byref(d), ctypes.c_void_p(stream)),
               "rt_temporal_async")
+
+    def resolve(self, cur, aov, spp, prev_view=None, now_rays=None, history=None, flags=0, **options):
+        """The clamped temporal resolve (rt_resolve, include/rt_resolve.h),
+        synchronously, on host arrays: cur (H, W, 3) float32 sums of this
+        frame, aov the dict Context.aov returns for this frame and the same
+        spp ("hits", "depth", "normal" are read), now_rays this frame's
+        resolve_rays, history the (3, H, W, 4) float32 array the previous
+        frame's call (or Context.temporal) returned and prev_view that frame's
+        temporal_view (both None: no history).  Options: RESOLVE_DEFAULTS (see
+        resolve_desc).  Returns (out, history_out) as Context.temporal;
+        self.resolve_ms holds the launch's event time."""
+        if (history is None) != (prev_view is None):
+            raise ValueError("history and prev_view go together")
+        d = resolve_desc(int(np.shape(cur)[1]), int(np.shape(cur)[0]), spp, prev_view, now_rays, flags, **options)
+        missing = [k for k in RESOLVE_BUFFERS[1:4] if k not in aov]
+        if missing:
+            raise ValueError(f"feature buffers {missing} are missing")
+        keep = {"cur": _frame_array("cur", cur, np.float32, d),
+                "hits": _frame_array("hits", aov["hits"], np.uint32, d, tail=()),
+                "depth": _frame_array("depth", aov["depth"], np.float32, d, tail=()),
+                "normal": _frame_array("normal", aov["normal"], np.float32, d)}
+        if history is not None:
+            keep["history_in"] = _frame_array("history_in", history, np.float32, d, lead=(3,), tail=(4,))
+        for k, a in keep.items():
+            setattr(d, k, a.ctypes.data)
+        out = np.zeros((d.height, d.width, 3), np.float32)
+        history_out = np.zeros((3, d.height, d.width, 4), np.float32)
+        d.out, d.history_out = out.ctypes.data, history_out.ctypes.data
+        ms = ctypes.c_double()
+        check(resolve_lib().rt_resolve(self._h, ctypes.byref(d), ctypes.byref(ms)), "rt_resolve")
+        self.resolve_ms = ms.value
+        return out, history_out
+
+    def resolve_async(self, dev_ptrs, width, height, spp, prev_view, now_rays, stream=0, flags=0, **options):
+        """Enqueue the pass (rt_resolve_async) on raw device pointers (e.g.
+        torch tensor.data_ptr()): dev_ptrs maps RESOLVE_BUFFERS to device
+        pointers ("history_in" and "out" may be left out or None; "out" must
+        not be the cur buffer; the histories are
+        temporal_lib().rt_temporal_history_bytes(width, height) bytes each and
+        must not overlap); prev_view: the view history_in was made with (None
+        without one); now_rays: this frame's resolve_rays."""
+        _reject_unknown(dev_ptrs, RESOLVE_BUFFERS, "resolve buffers")
+        d = resolve_desc(width, height, spp, prev_view, now_rays, flags, **options)
+        for name, ptr in dev_ptrs.items():
+            setattr(d, name, ptr)
+        check(resolve_lib().rt_resolve_async(self._h, ctypes.byref(d), ctypes.c_void_p(stream)),
+              "rt_resolve_async")
 
     def tonemap_async(self, dev_sums, n_pixels, spp, dev_out, mode=RT_TONEMAP_CPU, stream=0):
         """write_color on the device: fp32 sums -> bytes, both device pointers."""
