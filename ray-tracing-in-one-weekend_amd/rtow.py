@@ -30,6 +30,8 @@ DENOISE_LIB_PATH = os.path.join(HERE, "librtow_denoise.so")
 TEMPORAL_LIB_PATH = os.path.join(HERE, "librtow_temporal.so")
 # the clamped temporal resolve with centre reprojection (include/rt_resolve.h): a fifth
 RESOLVE_LIB_PATH = os.path.join(HERE, "librtow_resolve.so")
+# guided upsampling of a low-resolution frame (include/rt_upscale.h): a sixth
+UPSCALE_LIB_PATH = os.path.join(HERE, "librtow_upscale.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
@@ -63,6 +65,13 @@ RESOLVE_VERSION = 1  # include/rt_resolve.h RT_RESOLVE_VERSION
 RESOLVE_BUFFERS = ("cur", "hits", "depth", "normal", "history_in", "history_out", "out")
 RESOLVE_DEFAULTS = {"max_len": 2, "plane_tol": 0.003, "normal_cos": 0.9, "gamma": 1.0}
 RESOLVE_KEEP_PARTIAL = 1  # RT_RESOLVE_KEEP_PARTIAL
+UPSCALE_VERSION = 1  # include/rt_upscale.h RT_UPSCALE_VERSION
+# rt_upscale_desc's pointers in order (stage may be NULL; the albedos with UPSCALE_NO_ALBEDO), its options, its flags
+UPSCALE_INPUTS = ("cur", "hits_lo", "position_lo", "normal_lo", "albedo_lo",
+                  "hits_hi", "position_hi", "normal_hi", "albedo_hi")
+UPSCALE_BUFFERS = UPSCALE_INPUTS + ("out", "stage")
+UPSCALE_DEFAULTS = {"plane_tol": 0.1, "normal_cos": -0.5}
+UPSCALE_NO_ALBEDO = 1  # RT_UPSCALE_NO_ALBEDO
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
 RT_OPT_BVH_COLLAPSE, RT_OPT_BVH_SIDE, RT_OPT_LAUNCH_SAMPLES, RT_OPT_GRID_FIT = 4, 5, 6, 7
@@ -158,11 +167,22 @@ class ResolveDesc(ctypes.Structure):
                 [(name, ctypes.c_void_p) for name in RESOLVE_BUFFERS])
 
 
+class UpscaleDesc(ctypes.Structure):
+    """rt_upscale_desc: the two frames, the options (0 = default), the flags,
+    the low-resolution frame's view, the output frame's centre rays and device
+    (rt_upscale_async) or host (rt_upscale) pointers."""
+    _fields_ = ([(name, ctypes.c_int32) for name in ("lo_width", "lo_height", "lo_spp", "width", "height", "spp")] +
+                [("plane_tol", ctypes.c_float), ("normal_cos", ctypes.c_float), ("flags", ctypes.c_uint32),
+                 ("reserved", ctypes.c_int32), ("lo_view", TemporalView), ("rays", ResolveRays)] +
+                [(name, ctypes.c_void_p) for name in UPSCALE_BUFFERS])
+
+
 _lib = None
 _aov_lib = None
 _denoise_lib = None
 _temporal_lib = None
 _resolve_lib = None
+_upscale_lib = None
 
 
 def _missing(path):
@@ -300,6 +320,48 @@ def resolve_desc(width, height, spp, prev_view=None, now_rays=None, flags=0, **o
     if prev_view is not None:
         d.prev = as_temporal_view(prev_view)
     d.now = as_resolve_rays(now_rays)
+    return d
+
+
+def upscale_lib():
+    """Load librtow_upscale.so, guided upsampling of a low-resolution frame
+    (raises if it has not been built)."""
+    global _upscale_lib
+    if _upscale_lib is None:
+        _upscale_lib = _load_pass(UPSCALE_LIB_PATH, "rt_upscale_version", UPSCALE_VERSION, {
+            "rt_upscale_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+            "rt_upscale_async": (None, [ctypes.c_void_p, ctypes.POINTER(UpscaleDesc), ctypes.c_void_p,
+                                        ctypes.c_void_p]),
+            "rt_upscale": (None, [ctypes.c_void_p, ctypes.POINTER(UpscaleDesc), ctypes.POINTER(ctypes.c_double)])})
+    return _upscale_lib
+
+
+def upscale_scratch_bytes(lo_width, lo_height):
+    """rt_upscale_scratch_bytes: 48 * w * h, 0 for a size out of range."""
+    return upscale_lib().rt_upscale_scratch_bytes(lo_width, lo_height)
+
+
+def upscale_desc(lo_width, lo_height, lo_spp, width, height, spp, lo_view=None, rays=None, flags=0, **options):
+    """An UpscaleDesc without pointers.  Options (UPSCALE_DEFAULTS) left out or
+    None take their defaults; a value means itself: plane_tol=inf and
+    normal_cos=-1 switch their tests off.  The struct reads 0 as "default", so
+    an option of 0 cannot be asked for.  lo_view: temporal_view of the
+    low-resolution camera; rays: resolve_rays of the output's camera (the two
+    share the eye).  flags: UPSCALE_NO_ALBEDO or 0."""
+    _reject_unknown(options, UPSCALE_DEFAULTS, "upscale options")
+    opt = {k: v for k, v in options.items() if v is not None}
+    zero = [k for k, v in opt.items() if v == 0]
+    if zero:
+        raise ValueError(f"upscale options {zero} must not be 0 (the struct's 0 means the default)")
+    if lo_view is None or rays is None:
+        raise ValueError("lo_view (temporal_view of the low-resolution camera) and rays (resolve_rays of the "
+                         "output's camera) are required")
+    d = UpscaleDesc(lo_width=lo_width, lo_height=lo_height, lo_spp=lo_spp, width=width, height=height, spp=spp,
+                    flags=int(flags))
+    d.plane_tol = float(opt.get("plane_tol", 0.0))
+    d.normal_cos = float(opt.get("normal_cos", 0.0))
+    d.lo_view = as_temporal_view(lo_view)
+    d.rays = as_resolve_rays(rays)
     return d
 
 
@@ -792,6 +854,59 @@ class Context:
             setattr(d, name, ptr)
         check(resolve_lib().rt_resolve_async(self._h, ctypes.byref(d), ctypes.c_void_p(stream)),
               "rt_resolve_async")
+
+    def upscale(self, cur, aov_lo, lo_spp, aov_hi, spp, lo_view=None, rays=None, flags=0, want_stage=True,
+                **options):
+        """Guided upsampling (rt_upscale, include/rt_upscale.h), synchronously,
+        on host arrays: cur (h, w, 3) float32 sums of the low-resolution frame
+        over lo_spp samples, aov_lo the dict Context.aov returns for that frame
+        and aov_hi the one for the output frame, traced with spp ("hits",
+        "position", "normal" and, without UPSCALE_NO_ALBEDO, "albedo" are
+        read; the output's size is aov_hi's), lo_view the low-resolution
+        camera's temporal_view and rays the output camera's resolve_rays.
+        Options: UPSCALE_DEFAULTS (see upscale_desc).  Returns (out, stage):
+        the sums (H, W, 3) float32, mean x lo_spp, and which step produced
+        each pixel (H, W) uint8 (None with want_stage=False);
+        self.upscale_ms holds the launches' event time."""
+        names = ("hits", "position", "normal") + (() if int(flags) & UPSCALE_NO_ALBEDO else ("albedo",))
+        for what, aov in (("aov_lo", aov_lo), ("aov_hi", aov_hi)):
+            missing = [k for k in names if k not in aov]
+            if missing:
+                raise ValueError(f"feature buffers {missing} are missing in {what}")
+        d = upscale_desc(int(np.shape(cur)[1]), int(np.shape(cur)[0]), lo_spp, int(np.shape(aov_hi["hits"])[1]),
+                         int(np.shape(aov_hi["hits"])[0]), spp, lo_view, rays, flags, **options)
+        lo = DenoiseDesc(width=d.lo_width, height=d.lo_height)  # (the two frames, for _frame_array)
+        hi = DenoiseDesc(width=d.width, height=d.height)
+        keep = {"cur": _frame_array("cur", cur, np.float32, lo)}
+        for tag, aov, fr in (("lo", aov_lo, lo), ("hi", aov_hi, hi)):
+            keep["hits_" + tag] = _frame_array("hits_" + tag, aov["hits"], np.uint32, fr, tail=())
+            for k in names[1:]:
+                keep[f"{k}_{tag}"] = _frame_array(f"{k}_{tag}", aov[k], np.float32, fr)
+        for k, a in keep.items():
+            setattr(d, k, a.ctypes.data)
+        out = np.zeros((d.height, d.width, 3), np.float32)
+        stage = np.zeros((d.height, d.width), np.uint8) if want_stage else None
+        d.out = out.ctypes.data
+        if want_stage:
+            d.stage = stage.ctypes.data
+        ms = ctypes.c_double()
+        check(upscale_lib().rt_upscale(self._h, ctypes.byref(d), ctypes.byref(ms)), "rt_upscale")
+        self.upscale_ms = ms.value
+        return out, stage
+
+    def upscale_async(self, dev_ptrs, lo_width, lo_height, lo_spp, width, height, spp, lo_view, rays, scratch_ptr,
+                      stream=0, flags=0, **options):
+        """Enqueue the pass (rt_upscale_async) on raw device pointers (e.g.
+        torch tensor.data_ptr()): dev_ptrs maps UPSCALE_BUFFERS to device
+        pointers ("stage" may be left out or None, the albedos with
+        UPSCALE_NO_ALBEDO), scratch_ptr is upscale_scratch_bytes(lo_width,
+        lo_height) bytes, 16-byte aligned."""
+        _reject_unknown(dev_ptrs, UPSCALE_BUFFERS, "upscale buffers")
+        d = upscale_desc(lo_width, lo_height, lo_spp, width, height, spp, lo_view, rays, flags, **options)
+        for name, ptr in dev_ptrs.items():
+            setattr(d, name, ptr)
+        check(upscale_lib().rt_upscale_async(self._h, ctypes.byref(d), ctypes.c_void_p(scratch_ptr),
+                                             ctypes.c_void_p(stream)), "rt_upscale_async")
 
     def tonemap_async(self, dev_sums, n_pixels, spp, dev_out, mode=RT_TONEMAP_CPU, stream=0):
         """write_color on the device: fp32 sums -> bytes, both device pointers."""
