@@ -64,7 +64,8 @@
  *    frames of the final and the five-sphere scene against 4096-spp renders
  *    (DESIGN.md 10).
  *  - Known limitation.  The guides are first-hit: detail seen through glass
- *    or in a mirror has smooth guides, and only w_c protects it.
+ *    or in a mirror has smooth guides, and only w_c protects it.  rt_guides.h
+ *    gives buffers of the same layout that follow such paths to what is seen.
  *
  * A pass is serialised with the renders, feature passes and scene uploads of
  * its context, on whatever stream it runs; it needs no uploaded scene.  One

@@ -93,6 +93,9 @@
  *    through glass is validated against the mirror's or the glass's own
  *    surface, so reflections and refractions lag behind a moving camera by up
  *    to max_len frames.  There is no colour clamp in this version.
+ *    rt_guides.h gives buffers of the same layout that follow such paths to
+ *    what is seen (its position is the real surface's, not the virtual
+ *    image's: DESIGN.md 14 says what this pass would need).
  *
  * A pass is serialised with the renders, feature passes, filters and scene
  * uploads of its context, on whatever stream it runs; it needs no uploaded

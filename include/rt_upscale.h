@@ -88,6 +88,8 @@
  *  - Known limitation.  The guides are first-hit: what is seen in a mirror or
  *    through glass has the mirror's or the glass's own smooth guides, so
  *    reflections and refractions are upsampled as plain bilinear detail.
+ *    rt_guides.h gives buffers of the same layout that follow such paths to
+ *    what is seen.
  *
  * A pass is serialised with the renders, feature passes, filters and scene
  * uploads of its context, on whatever stream it runs; it needs no uploaded

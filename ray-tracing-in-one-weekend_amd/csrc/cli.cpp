@@ -15,7 +15,7 @@
 //   extent; 11 = reference, 50 = 10k spheres) --scene final|five
 //   --camera cpu|gpu --semantics cpu|gpu --accel bvh|scan --gpus N --device N
 //   --devices D0,D1,... --gather rccl|host --out FILE --p6 --quiet
-//   --denoise[=ITERATIONS]
+//   --denoise[=ITERATIONS] --denoise-guides=first|chain
 // With --gpus N > 1 the frame is split into interleaved 8-row bands, one
 // context and stream per device; each device tonemaps its tile to bytes
 // (rt_tonemap_async) and the byte tiles are gathered to device 0 with one
@@ -29,6 +29,9 @@
 // with the first-hit feature pass at the same parameters (rt_aov.h) and the
 // guided a-trous filter (rt_denoise.h, its default options), in place, on the
 // same stream; write_color and the PPM path then run on the filtered sums.
+// --denoise-guides=chain (with --denoise only) guides the filter with rt_guides
+// at its defaults (rt_guides.h: the buffers follow mirror and glass paths)
+// instead of rt_aov; first, the default, is rt_aov.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -48,6 +51,7 @@
 #include "rt.h"
 #include "rt_aov.h"
 #include "rt_denoise.h"
+#include "rt_guides.h"
 
 namespace {
 
@@ -68,6 +72,7 @@ struct options {
   double launch_samples = 0.0;  // RT_OPT_LAUNCH_SAMPLES (0: the library's default)
   bool denoise = false;
   int denoise_iterations = 0;  // --denoise=N (0: the library's default)
+  bool guides_set = false, guides_chain = false;  // --denoise-guides=first|chain
 };
 
 [[noreturn]] void die(const char *what, int st) {
@@ -85,7 +90,7 @@ void check(int st, const char *what) {
                "          [--spheres HALF_EXTENT] [--scene final|five] [--camera cpu|gpu]\n"
                "          [--semantics cpu|gpu] [--accel bvh|scan] [--gpus N] [--device N]\n"
                "          [--devices D0,D1,...] [--gather rccl|host] [--out FILE] [--p6] [--quiet]\n"
-               "          [--launch-samples N] [--denoise[=ITERATIONS]]\n",
+               "          [--launch-samples N] [--denoise[=ITERATIONS]] [--denoise-guides=first|chain]\n",
                argv0);
   std::exit(2);
 }
@@ -144,6 +149,12 @@ int main(int argc, char **argv) {
     else if (a == "--quiet") o.quiet = true;
     else if (a == "--launch-samples") o.launch_samples = std::atof(next());
     else if (a == "--denoise") o.denoise = true;
+    else if (a.rfind("--denoise-guides=", 0) == 0) {
+      const std::string v = a.substr(17);
+      if (v != "first" && v != "chain") usage(argv[0]);
+      o.guides_set = true;
+      o.guides_chain = v == "chain";
+    }
     else if (a.rfind("--denoise=", 0) == 0) {
       o.denoise = true;
       o.denoise_iterations = std::atoi(a.c_str() + 10);
@@ -164,6 +175,7 @@ int main(int argc, char **argv) {
     std::exit(2);
   }
   if (o.denoise && o.spp < 1) usage(argv[0]);
+  if (o.guides_set && !o.denoise) usage(argv[0]);  // the guides are the filter's
   bool repeated = false;
   if (!o.devices.empty()) {
     if ((int)o.devices.size() != o.gpus) usage(argv[0]);
@@ -331,7 +343,16 @@ int main(int argc, char **argv) {
       gb.position = reinterpret_cast<float *>(d_guides + 4 * tile_px);
       gb.normal = gb.position + 3 * tile_px;
       gb.albedo = gb.normal + 3 * tile_px;
-      check(rt_aov_async(ctxs[g], &cam, &jobs[g].params, &gb, streams[g]), "rt_aov_async");
+      if (o.guides_chain) {
+        rt_guides_buffers cb{};
+        cb.hits = gb.hits;
+        cb.position = gb.position;
+        cb.normal = gb.normal;
+        cb.albedo = gb.albedo;
+        check(rt_guides_async(ctxs[g], &cam, &jobs[g].params, nullptr, &cb, streams[g]), "rt_guides_async");
+      } else {
+        check(rt_aov_async(ctxs[g], &cam, &jobs[g].params, &gb, streams[g]), "rt_aov_async");
+      }
       rt_denoise_desc dd{};
       dd.width = o.width;
       dd.height = o.height;

@@ -1,12 +1,14 @@
 // rt_frame.h -- internal: how a pass of a context starts and ends on a stream,
 // and the host helpers its passes share.  A pass over the context's scene (the
 // render in rt_api.cpp, the first-hit feature pass in rt_aov.hip /
-// librtow_aov.so) begins with rt_internal_frame_begin; an image-space pass
+// librtow_aov.so, the chain-following one in rt_guides.hip /
+// librtow_guides.so) begins with rt_internal_frame_begin; an image-space pass
 // that only shares the context's ordering (the denoiser in rt_denoise.hip /
 // librtow_denoise.so, temporal accumulation in rt_temporal.hip /
 // librtow_temporal.so) with rt_internal_pass_begin.  The helpers: hip_fail /
 // RT_HIP, rt_pass_scope, rt_device_buf and rt_sync_pass, the one
-// host sequence of the synchronous rt_aov / rt_denoise / rt_temporal.  Not
+// host sequence of the synchronous rt_aov / rt_denoise / rt_temporal /
+// rt_resolve / rt_upscale / rt_guides.  Not
 // installed; rt_context stays opaque outside rt_api.cpp, so the other
 // libraries get what they need through rt_frame_setup.
 #ifndef RTOW_RT_FRAME_H

@@ -14,6 +14,7 @@ Reference anchors:
   write_ppm()     main.cc:109 / output_image src/gpu/camera.h:197-210
 """
 import ctypes
+import math
 import os
 from dataclasses import dataclass
 
@@ -32,6 +33,8 @@ TEMPORAL_LIB_PATH = os.path.join(HERE, "librtow_temporal.so")
 RESOLVE_LIB_PATH = os.path.join(HERE, "librtow_resolve.so")
 # guided upsampling of a low-resolution frame (include/rt_upscale.h): a sixth
 UPSCALE_LIB_PATH = os.path.join(HERE, "librtow_upscale.so")
+# feature buffers that follow mirror and glass paths (include/rt_guides.h): a seventh
+GUIDES_LIB_PATH = os.path.join(HERE, "librtow_guides.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
@@ -72,6 +75,11 @@ UPSCALE_INPUTS = ("cur", "hits_lo", "position_lo", "normal_lo", "albedo_lo",
 UPSCALE_BUFFERS = UPSCALE_INPUTS + ("out", "stage")
 UPSCALE_DEFAULTS = {"plane_tol": 0.1, "normal_cos": -0.5}
 UPSCALE_NO_ALBEDO = 1  # RT_UPSCALE_NO_ALBEDO
+GUIDES_VERSION = 1  # include/rt_guides.h RT_GUIDES_VERSION
+# rt_guides_buffers' fields in order: rt_aov_buffers', then the two counts; the options with their defaults
+GUIDES_FIELDS = AOV_FIELDS + (("bounces", np.uint32, 1), ("escaped", np.uint32, 1))
+GUIDES_DEFAULTS = {"max_bounces": 8, "max_fuzz": 0.0}
+GUIDES_MAX_BOUNCES = 64
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
 RT_OPT_BVH_COLLAPSE, RT_OPT_BVH_SIDE, RT_OPT_LAUNCH_SAMPLES, RT_OPT_GRID_FIT = 4, 5, 6, 7
@@ -125,6 +133,16 @@ class Stats(ctypes.Structure):
 class AovBuffers(ctypes.Structure):
     """rt_aov_buffers: device (rt_aov_async) or host (rt_aov) pointers, NULL = not wanted."""
     _fields_ = [(name, ctypes.c_void_p) for name, _, _ in AOV_FIELDS]
+
+
+class GuidesBuffers(ctypes.Structure):
+    """rt_guides_buffers: device (rt_guides_async) or host (rt_guides) pointers, NULL = not wanted."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in GUIDES_FIELDS]
+
+
+class GuidesOptions(ctypes.Structure):
+    """rt_guides_options: max_bounces (0 = default, -1 = none), max_fuzz, reserved."""
+    _fields_ = [("max_bounces", ctypes.c_int32), ("max_fuzz", ctypes.c_float), ("reserved", ctypes.c_uint32)]
 
 
 class DenoiseDesc(ctypes.Structure):
@@ -183,6 +201,7 @@ _denoise_lib = None
 _temporal_lib = None
 _resolve_lib = None
 _upscale_lib = None
+_guides_lib = None
 
 
 def _missing(path):
@@ -393,6 +412,38 @@ def denoise_desc(width, height, spp, **options):
     d.sigma_plane = float(opt.get("sigma_plane", 0.0))
     d.sigma_color = (float(opt["sigma_color"]) or -1.0) if "sigma_color" in opt else 0.0
     return d
+
+
+def guides_lib():
+    """Load librtow_guides.so, the feature pass that follows mirror and glass
+    paths (raises if it has not been built)."""
+    global _guides_lib
+    if _guides_lib is None:
+        head = [ctypes.c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Params), ctypes.POINTER(GuidesOptions),
+                ctypes.POINTER(GuidesBuffers)]
+        _guides_lib = _load_pass(GUIDES_LIB_PATH, "rt_guides_version", GUIDES_VERSION, {
+            "rt_guides_async": (None, head + [ctypes.c_void_p]),
+            "rt_guides": (None, head + [ctypes.POINTER(ctypes.c_double)])})
+    return _guides_lib
+
+
+def guides_options(max_bounces=None, max_fuzz=None):
+    """A GuidesOptions.  None takes the default (GUIDES_DEFAULTS); a value means
+    itself: max_bounces=0 follows nothing (rt_aov's buffers; the struct spells
+    it -1, its own 0 being the default), 1..GUIDES_MAX_BOUNCES bounds the
+    chain; max_fuzz >= 0 is the roughest metal that still continues it."""
+    o = GuidesOptions()
+    if max_bounces is not None:
+        if isinstance(max_bounces, bool) or not math.isfinite(max_bounces) or int(max_bounces) != max_bounces:
+            raise ValueError("max_bounces must be an integer")
+        if not 0 <= max_bounces <= GUIDES_MAX_BOUNCES:
+            raise ValueError(f"max_bounces must be in 0..{GUIDES_MAX_BOUNCES}")
+        o.max_bounces = int(max_bounces) or -1
+    if max_fuzz is not None:
+        if not float(max_fuzz) >= 0.0:
+            raise ValueError("max_fuzz must be >= 0")
+        o.max_fuzz = float(max_fuzz)
+    return o
 
 
 def aov_lib():
@@ -724,6 +775,38 @@ class Context:
             setattr(bufs, name, ptr)
         check(aov_lib().rt_aov_async(self._h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(bufs),
                                      ctypes.c_void_p(stream)), "rt_aov_async")
+
+    def guides(self, cam, params, which=tuple(f[0] for f in GUIDES_FIELDS), max_bounces=None, max_fuzz=None):
+        """Feature buffers that follow each sample's path through mirrors and
+        glass to the first rough surface (rt_guides, include/rt_guides.h),
+        synchronously: Context.aov's dict (the same keys, layout and sum
+        contract, so denoise / temporal / resolve / upscale take it as it is)
+        plus "bounces" and "escaped".  Options: see guides_options."""
+        _reject_unknown(which, [f[0] for f in GUIDES_FIELDS], "feature buffers")
+        opts = guides_options(max_bounces, max_fuzz)
+        out, bufs = {}, GuidesBuffers()
+        for name, dt, ch in GUIDES_FIELDS:
+            if name in which:
+                shape = (params.local_rows, params.width) + ((3,) if ch == 3 else ())
+                out[name] = np.zeros(shape, dt)
+                setattr(bufs, name, out[name].ctypes.data)
+        ms = ctypes.c_double()
+        check(guides_lib().rt_guides(self._h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(opts),
+                                     ctypes.byref(bufs), ctypes.byref(ms)), "rt_guides")
+        out["kernel_ms"] = ms.value
+        return out
+
+    def guides_async(self, cam, params, dev_ptrs, stream=0, max_bounces=None, max_fuzz=None):
+        """Enqueue the pass (rt_guides_async) into raw device pointers (e.g.
+        torch tensor.data_ptr()): dev_ptrs maps names of GUIDES_FIELDS to device
+        pointers; names left out are not computed."""
+        _reject_unknown(dev_ptrs, [f[0] for f in GUIDES_FIELDS], "feature buffers")
+        opts = guides_options(max_bounces, max_fuzz)
+        bufs = GuidesBuffers()
+        for name, ptr in dev_ptrs.items():
+            setattr(bufs, name, ptr)
+        check(guides_lib().rt_guides_async(self._h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(opts),
+                                           ctypes.byref(bufs), ctypes.c_void_p(stream)), "rt_guides_async")
 
     def denoise(self, beauty, aov, spp, **options):
         """The guided a-trous filter (rt_denoise, include/rt_denoise.h),
