@@ -5,7 +5,10 @@
 // librtow_guides.so) begins with rt_internal_frame_begin; an image-space pass
 // that only shares the context's ordering (the denoiser in rt_denoise.hip /
 // librtow_denoise.so, temporal accumulation in rt_temporal.hip /
-// librtow_temporal.so) with rt_internal_pass_begin.  The helpers: hip_fail /
+// librtow_temporal.so, the resolve in rt_resolve.hip / librtow_resolve.so,
+// upsampling in rt_upscale.hip / librtow_upscale.so) with
+// rt_internal_pass_begin; what those share beyond this header is in rt_post.h
+// and rt_reproject.h.  The helpers: hip_fail /
 // RT_HIP, rt_pass_scope, rt_device_buf and rt_sync_pass, the one
 // host sequence of the synchronous rt_aov / rt_denoise / rt_temporal /
 // rt_resolve / rt_upscale / rt_guides.  Not

@@ -1,10 +1,13 @@
 // rt_post.h -- internal: what the image-space passes over the rt_aov sums
-// (the denoiser in rt_denoise.hip, temporal accumulation in rt_temporal.hip)
-// share on the device -- the global address space, the unfused dot product,
-// the 16 x 16 pixel tile, the frame size limit and the guide preparation.
+// (the denoiser in rt_denoise.hip, temporal accumulation in rt_temporal.hip,
+// the resolve in rt_resolve.hip, upsampling in rt_upscale.hip) share -- on the
+// device the global address space, the unfused dot product, the 16 x 16 pixel
+// tile and the guide preparation; on the host the frame size limit and the
+// argument rules (overlap, alignment, "0 = default" options).  What only the
+// passes that reproject share is in rt_reproject.h, which includes this.
 //
 // Their arithmetic is written operation by operation, without fmaf, so that
-// the numpy restatements (tests/post_ref.py and its two users) round the same
+// the numpy restatements (tests/post_ref.py and its users) round the same
 // way.  csrc/rt_device.h's dot3 is the fused one: this header does not include
 // it, and a pass that includes this one compiles none of the render's device
 // helpers and no g_turn_tab.
@@ -32,6 +35,22 @@ constexpr int kPostMaxDim = 32768;
 inline bool post_size_ok(int w, int h) { return w >= 1 && h >= 1 && w <= kPostMaxDim && h <= kPostMaxDim; }
 inline dim3 post_grid(int w, int h) {
   return dim3((unsigned)((w + kPostTile - 1) / kPostTile), (unsigned)((h + kPostTile - 1) / kPostTile));
+}
+
+// The argument rules the passes' resolve() functions share.
+// np bytes at p and nq bytes at q have a byte in common (neither NULL)
+inline bool overlap(const void *p, size_t np, const void *q, size_t nq) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return p && q && a < b + nq && b < a + np;
+}
+// a buffer read and written as float4 (NULL passes)
+inline bool post_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+// An option of a desc, where 0 asks for the default: v, the effective value.
+// false: v lies outside lo .. hi (lo itself only where lo_in), or is NaN
+template <typename T>
+inline bool post_option(T given, T dflt, T lo, bool lo_in, T hi, T &v) {
+  v = given == T(0) ? dflt : given;
+  return (lo_in ? v >= lo : v > lo) && v <= hi;
 }
 
 // the pixel of this lane in a post_grid launch of 256 threads; false: outside the frame

@@ -7,7 +7,9 @@
 // point it projects through the previous view lies on the pixel centre's ray
 // at the mean first-hit depth; a partly covered pixel restarts; and the
 // gathered history colour is clamped to the mean +- gamma standard deviations
-// of the 3 x 3 neighbourhood of this frame's colour.  The nine neighbourhood
+// of the 3 x 3 neighbourhood of this frame's colour.  Those three are what
+// this file holds; the projection, the gather, the blend and the history
+// write are the one copy in csrc/rt_reproject.h.  The nine neighbourhood
 // reads come from the vector cache: each is a load from a
 // CLAMPED pixel coordinate, so it is unconditional and never leaves the frame,
 // and a pixel outside the frame is dropped by a select, not by a branch.
@@ -27,7 +29,7 @@
 
 #include "rt_resolve.h"
 #include "rt_frame.h"
-#include "rt_post.h"
+#include "rt_reproject.h"
 
 namespace rtk {
 
@@ -35,17 +37,11 @@ constexpr int kRsDefaultMaxLen = 2, kRsMaxMaxLen = 1024;
 constexpr float kRsDefaultPlaneTol = 0.003f, kRsDefaultNormalCos = 0.9f, kRsDefaultGamma = 1.0f;
 
 struct rs_params {
-  int width, height;
-  float width_f, height_f;
-  float spp_f;
+  rp_params h;
   uint32_t spp;
-  float max_len_f;
-  float pt2;         // plane_tol^2
-  float normal_cos;
   float gamma;
-  int plane_test, normal_test, clamp;  // 0: the step is left out
+  int clamp;  // 0: the step is left out
   int keep_partial;
-  rt_temporal_view prev;
   rt_resolve_rays now;
   // the caller's sums
   const float *cur;
@@ -60,30 +56,26 @@ struct rs_params {
 // the lanes that go on to look a history up.
 __global__ __launch_bounds__(256) void resolve_kernel(const rs_params a) {
   int x, y;
-  if (!post_pixel(a.width, a.height, x, y)) return;
-  const size_t npx = (size_t)a.width * (size_t)a.height;
-  const size_t o = (size_t)y * (size_t)a.width + (size_t)x;
+  if (!post_pixel(a.h.width, a.h.height, x, y)) return;
+  const size_t npx = (size_t)a.h.width * (size_t)a.h.height;
+  const size_t o = (size_t)y * (size_t)a.h.width + (size_t)x;
   // 1. prepare
   const RT_GLOBAL float *g_cur = as_global(a.cur);
   const RT_GLOBAL float *g_c = g_cur + 3 * o;
   const RT_GLOBAL float *g_n = as_global(a.normal) + 3 * o;
   const uint32_t h = as_global(a.hits)[o];
-  const float cr = g_c[0] / a.spp_f, cg = g_c[1] / a.spp_f, cb = g_c[2] / a.spp_f;
-  const post_guide g = post_prepare(h, g_n, g_n);  // its normal half: the position half is unused and compiled away
-  const bool sky = g.sky;
-  const float nx = g.nx, ny = g.ny, nz = g.nz;
+  const float cr = g_c[0] / a.h.spp_f, cg = g_c[1] / a.h.spp_f, cb = g_c[2] / a.h.spp_f;
+  post_guide g = post_prepare(h, g_n, g_n);  // its normal half: the position half is compiled away, and set below
   const float tm = as_global(a.depth)[o] / (float)h;
-  const float xf_ = (float)x, yf_ = (float)y;
-  const float Dx = (a.now.d00[0] + xf_ * a.now.du[0]) + yf_ * a.now.dv[0];
-  const float Dy = (a.now.d00[1] + xf_ * a.now.du[1]) + yf_ * a.now.dv[1];
-  const float Dz = (a.now.d00[2] + xf_ * a.now.du[2]) + yf_ * a.now.dv[2];
-  const float dl = __builtin_sqrtf(dot3_unfused(Dx, Dy, Dz, Dx, Dy, Dz));
-  const float Px = sky ? 0.0f : a.now.eye[0] + (Dx / dl) * tm;
-  const float Py = sky ? 0.0f : a.now.eye[1] + (Dy / dl) * tm;
-  const float Pz = sky ? 0.0f : a.now.eye[2] + (Dz / dl) * tm;
+  float D[3];
+  rp_centre_ray(a.now, x, y, D);
+  const float dl = __builtin_sqrtf(dot3_unfused(D[0], D[1], D[2], D[0], D[1], D[2]));
+  g.px = g.sky ? 0.0f : a.now.eye[0] + (D[0] / dl) * tm;
+  g.py = g.sky ? 0.0f : a.now.eye[1] + (D[1] / dl) * tm;
+  g.pz = g.sky ? 0.0f : a.now.eye[2] + (D[2] / dl) * tm;
   // 3. no history
   float mr = cr, mg = cg, mb = cb, len = 1.0f;
-  if (a.hist_in && !sky && (a.keep_partial || h >= a.spp)) {
+  if (a.hist_in && !g.sky && (a.keep_partial || h >= a.spp)) {
     // 2. neighbourhood: unconditional loads from clamped coordinates, selects
     float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {0.0f, 0.0f, 0.0f};
     if (a.clamp) {
@@ -91,16 +83,16 @@ __global__ __launch_bounds__(256) void resolve_kernel(const rs_params a) {
 #pragma unroll
       for (int dy = -1; dy <= 1; ++dy) {
         const int ty = y + dy;
-        const bool iny = ty >= 0 && ty < a.height;
-        const size_t row = (size_t)(iny ? ty : y) * (size_t)a.width;
+        const bool iny = ty >= 0 && ty < a.h.height;
+        const size_t row = (size_t)(iny ? ty : y) * (size_t)a.h.width;
 #pragma unroll
         for (int dx = -1; dx <= 1; ++dx) {
           const int tx = x + dx;
-          const bool in = iny && tx >= 0 && tx < a.width;
+          const bool in = iny && tx >= 0 && tx < a.h.width;
           const RT_GLOBAL float *q = g_cur + 3 * (row + (size_t)(in ? tx : x));
 #pragma unroll
           for (int ch = 0; ch < 3; ++ch) {
-            const float cq = q[ch] / a.spp_f;
+            const float cq = q[ch] / a.h.spp_f;
             m1[ch] = in ? m1[ch] + cq : m1[ch];
             m2[ch] = in ? m2[ch] + cq * cq : m2[ch];
           }
@@ -118,86 +110,23 @@ __global__ __launch_bounds__(256) void resolve_kernel(const rs_params a) {
       }
     }
     // 4. reproject and gather (rt_temporal.h, steps 3 and 4)
-    const float qx = Px - a.prev.eye[0], qy = Py - a.prev.eye[1], qz = Pz - a.prev.eye[2];
-    const float w = dot3_unfused(a.prev.pw[0], a.prev.pw[1], a.prev.pw[2], qx, qy, qz);
-    const float fxp = dot3_unfused(a.prev.px[0], a.prev.px[1], a.prev.px[2], qx, qy, qz) / w - a.prev.x0;
-    const float fyp = dot3_unfused(a.prev.py[0], a.prev.py[1], a.prev.py[2], qx, qy, qz) / w - a.prev.y0;
-    const bool ok = w > 0.0f && fxp > -1.0f && fxp < a.width_f && fyp > -1.0f && fyp < a.height_f;
-    if (ok) {
-      const float xf = __builtin_floorf(fxp), yf = __builtin_floorf(fyp);
-      const float fx = fxp - xf, fy = fyp - yf;
-      const int xi = (int)xf, yi = (int)yf;  // -1 .. W-1, -1 .. H-1
-      const float d2 = dot3_unfused(qx, qy, qz, qx, qy, qz);
-      const float lim = a.pt2 * d2;
-      const RT_GLOBAL f4 *__restrict__ h0 = as_global(a.hist_in);
-      const RT_GLOBAL f4 *__restrict__ h1 = h0 + npx;
-      const RT_GLOBAL f4 *__restrict__ h2 = h1 + npx;
-      float sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f, sw = 0.0f;
-#pragma unroll
-      for (int dy = 0; dy <= 1; ++dy) {
-#pragma unroll
-        for (int dx = 0; dx <= 1; ++dx) {
-          const int tx = xi + dx, ty = yi + dy;
-          if (tx < 0 || tx >= a.width || ty < 0 || ty >= a.height) continue;
-          const size_t t = (size_t)ty * (size_t)a.width + (size_t)tx;
-          const f4 pt = h1[t];
-          if (pt.w != 0.0f) continue;
-          const f4 nt = h2[t];
-          const float e = dot3_unfused(nx, ny, nz, pt.x - Px, pt.y - Py, pt.z - Pz);
-          if (a.plane_test && !(e * e <= lim)) continue;
-          const float g = dot3_unfused(nx, ny, nz, nt.x, nt.y, nt.z);
-          if (a.normal_test && !(g >= a.normal_cos)) continue;
-          const f4 ct = h0[t];
-          const float b = (dx ? fx : 1.0f - fx) * (dy ? fy : 1.0f - fy);
-          sw += b;
-          sr += b * ct.x;
-          sg += b * ct.y;
-          sb += b * ct.z;
-          sl += b * ct.w;
-        }
+    const float qx = g.px - a.h.prev.eye[0], qy = g.py - a.h.prev.eye[1], qz = g.pz - a.h.prev.eye[2];
+    float w, fxp, fyp;
+    rp_project(a.h.prev, qx, qy, qz, w, fxp, fyp);
+    const rp_taps s = rp_gather(a.h, w, fxp, fyp, g, a.h.pt2 * dot3_unfused(qx, qy, qz, qx, qy, qz), a.hist_in);
+    // 5. clamp and blend
+    if (s.w > 0.0f) {
+      float hr = s.r / s.w, hg = s.g / s.w, hb = s.b / s.w;
+      if (a.clamp) {
+        hr = hr < lo[0] ? lo[0] : (hr > hi[0] ? hi[0] : hr);
+        hg = hg < lo[1] ? lo[1] : (hg > hi[1] ? hi[1] : hg);
+        hb = hb < lo[2] ? lo[2] : (hb > hi[2] ? hi[2] : hb);
       }
-      // 5. blend
-      if (sw > 0.0f) {
-        float hr = sr / sw, hg = sg / sw, hb = sb / sw;
-        const float hl = sl / sw;
-        if (a.clamp) {
-          hr = hr < lo[0] ? lo[0] : (hr > hi[0] ? hi[0] : hr);
-          hg = hg < lo[1] ? lo[1] : (hg > hi[1] ? hi[1] : hg);
-          hb = hb < lo[2] ? lo[2] : (hb > hi[2] ? hi[2] : hb);
-        }
-        const float t = hl + 1.0f;
-        len = t < a.max_len_f ? t : a.max_len_f;
-        const float al = 1.0f / len;
-        mr = hr + (cr - hr) * al;
-        mg = hg + (cg - hg) * al;
-        mb = hb + (cb - hb) * al;
-      }
+      rp_blend(hr, hg, hb, s.l / s.w, cr, cg, cb, a.h.max_len_f, mr, mg, mb, len);
     }
   }
   // 6. write
-  RT_GLOBAL f4 *o0 = as_global(a.hist_out);
-  f4 v;
-  v.x = mr;
-  v.y = mg;
-  v.z = mb;
-  v.w = len;
-  o0[o] = v;
-  v.x = Px;
-  v.y = Py;
-  v.z = Pz;
-  v.w = sky ? 1.0f : 0.0f;
-  o0[npx + o] = v;
-  v.x = nx;
-  v.y = ny;
-  v.z = nz;
-  v.w = 0.0f;
-  o0[2 * npx + o] = v;
-  if (a.out) {
-    RT_GLOBAL float *out = as_global(a.out) + 3 * o;
-    out[0] = mr * a.spp_f;
-    out[1] = mg * a.spp_f;
-    out[2] = mb * a.spp_f;
-  }
+  rp_write(a.hist_out, a.out, npx, o, 3 * o, mr, mg, mb, len, g, a.h.spp_f);
 }
 
 }  // namespace rtk
@@ -210,10 +139,7 @@ struct rs_options {
   float plane_tol, normal_cos, gamma;
 };
 
-bool overlap(const void *p, size_t np, const void *q, size_t nq) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return p && q && a < b + nq && b < a + np;
-}
+using rtk::overlap;
 
 // false: an argument is NULL, out of range or NaN, or the buffers overlap.
 // same_ok: out == cur is allowed (the synchronous wrapper stages out apart)
@@ -221,14 +147,11 @@ bool resolve(const rt_resolve_desc *d, rs_options &o, bool same_ok) {
   if (!rtk::post_size_ok(d->width, d->height)) return false;
   if (d->spp < 1 || d->reserved != 0 || (d->flags & ~RT_RESOLVE_KEEP_PARTIAL) != 0) return false;
   if (!d->cur || !d->hits || !d->depth || !d->normal || !d->history_out) return false;
-  o.max_len = d->max_len == 0 ? rtk::kRsDefaultMaxLen : d->max_len;
-  if (o.max_len < 1 || o.max_len > rtk::kRsMaxMaxLen) return false;
-  o.plane_tol = d->plane_tol == 0.0f ? rtk::kRsDefaultPlaneTol : d->plane_tol;
-  if (!(o.plane_tol > 0.0f)) return false;  // (NaN too)
-  o.normal_cos = d->normal_cos == 0.0f ? rtk::kRsDefaultNormalCos : d->normal_cos;
-  if (!(o.normal_cos >= -1.0f && o.normal_cos <= 1.0f)) return false;
-  o.gamma = d->gamma == 0.0f ? rtk::kRsDefaultGamma : d->gamma;
-  if (!(o.gamma > 0.0f)) return false;
+  if (!rtk::post_option(d->max_len, rtk::kRsDefaultMaxLen, 1, true, rtk::kRsMaxMaxLen, o.max_len) ||
+      !rtk::post_option(d->plane_tol, rtk::kRsDefaultPlaneTol, 0.0f, false, INFINITY, o.plane_tol) ||
+      !rtk::post_option(d->normal_cos, rtk::kRsDefaultNormalCos, -1.0f, true, 1.0f, o.normal_cos) ||
+      !rtk::post_option(d->gamma, rtk::kRsDefaultGamma, 0.0f, false, INFINITY, o.gamma))
+    return false;
   const size_t npx = (size_t)d->width * (size_t)d->height, hb = 48 * npx;
   if (overlap(d->history_out, hb, d->history_in, hb) || overlap(d->history_out, hb, d->cur, 12 * npx) ||
       overlap(d->history_out, hb, d->out, 12 * npx) || overlap(d->history_out, hb, d->hits, 4 * npx) ||
@@ -243,21 +166,11 @@ bool resolve(const rt_resolve_desc *d, rs_options &o, bool same_ok) {
 int enqueue(const rt_resolve_desc *d, const rs_options &o, hipStream_t st) {
   rtk::rs_params a;
   std::memset(&a, 0, sizeof a);
-  a.width = d->width;
-  a.height = d->height;
-  a.width_f = (float)d->width;
-  a.height_f = (float)d->height;
-  a.spp_f = (float)d->spp;
+  rtk::rp_fill(a.h, d->width, d->height, d->spp, o.max_len, o.plane_tol, o.normal_cos, d->prev);
   a.spp = (uint32_t)d->spp;
-  a.max_len_f = (float)o.max_len;
-  a.pt2 = o.plane_tol * o.plane_tol;
-  a.normal_cos = o.normal_cos;
   a.gamma = o.gamma;
-  a.plane_test = !std::isinf(o.plane_tol);
-  a.normal_test = o.normal_cos != -1.0f;
   a.clamp = !std::isinf(o.gamma);
   a.keep_partial = (d->flags & RT_RESOLVE_KEEP_PARTIAL) != 0;
-  a.prev = d->prev;
   a.now = d->now;
   a.cur = d->cur;
   a.hits = d->hits;
@@ -278,9 +191,7 @@ extern "C" {
 int rt_resolve_version(void) { return RT_RESOLVE_VERSION; }
 
 int rt_resolve_rays_from_camera(const rt_camera *cam, int width, int height, rt_resolve_rays *out) {
-  if (!cam || !out || !rtk::post_size_ok(width, height)) return RT_ERR_INVALID;
-  if (cam->model != RT_CAMERA_CPU && cam->model != RT_CAMERA_GPU) return RT_ERR_INVALID;
-  if (cam->model == RT_CAMERA_CPU && (width < 2 || height < 2)) return RT_ERR_INVALID;
+  if (!out || !rtk::rp_camera_ok(cam, width, height)) return RT_ERR_INVALID;
   // D = c + a0 horiz + b0 vert + i (sa horiz) + j (sb vert)
   double a0 = 0.0, b0 = 0.0, sa = 1.0, sb = 1.0;
   if (cam->model == RT_CAMERA_CPU) {
@@ -309,7 +220,7 @@ int rt_resolve_rays_from_camera(const rt_camera *cam, int width, int height, rt_
 int rt_resolve_async(rt_context *c, const rt_resolve_desc *d, void *stream) {
   rs_options o;
   if (!c || !d || !resolve(d, o, false)) return RT_ERR_INVALID;
-  if (((uintptr_t)d->history_in & 15) || ((uintptr_t)d->history_out & 15)) return RT_ERR_INVALID;
+  if (!rtk::post_aligned16(d->history_in) || !rtk::post_aligned16(d->history_out)) return RT_ERR_INVALID;
   rt_pass_scope ps(c, nullptr, nullptr, stream);
   return ps.end(ps.status == RT_OK ? enqueue(d, o, ps.fs.stream) : ps.status);
 }

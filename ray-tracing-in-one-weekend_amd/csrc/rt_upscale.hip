@@ -6,7 +6,8 @@
 // (demodulated colour + sky flag, mean position, unit normal), so that a tap
 // of the second launch is three 16-byte loads.  upscale_kernel runs one lane
 // per output pixel on the 16 x 16 tile: it prepares the pixel's own guides,
-// maps its centre ray through the low-resolution view and gathers the taps.
+// maps its centre ray through the low-resolution view (both steps are
+// csrc/rt_reproject.h's, shared with rt_resolve.hip) and gathers the taps.
 // The taps are read through the vector cache, not staged in LDS (DESIGN.md
 // 13): a tile's footprint in the low-resolution frame depends on the two
 // cameras, not on a fixed ratio, and at 2 x its 10 x 10 pixels of three planes
@@ -32,7 +33,7 @@
 
 #include "rt_upscale.h"
 #include "rt_frame.h"
-#include "rt_post.h"
+#include "rt_reproject.h"
 
 namespace rtk {
 
@@ -163,13 +164,10 @@ __global__ __launch_bounds__(256) void upscale_kernel(const up_params a) {
     mb = up_demod(g_a[2], h, a.spp, a.spp_f);
   }
   // 2. map the pixel into the low-resolution frame
-  const float xf_ = (float)x, yf_ = (float)y;
-  const float Dx = (a.rays.d00[0] + xf_ * a.rays.du[0]) + yf_ * a.rays.dv[0];
-  const float Dy = (a.rays.d00[1] + xf_ * a.rays.du[1]) + yf_ * a.rays.dv[1];
-  const float Dz = (a.rays.d00[2] + xf_ * a.rays.du[2]) + yf_ * a.rays.dv[2];
-  const float wq = dot3_unfused(a.lo_view.pw[0], a.lo_view.pw[1], a.lo_view.pw[2], Dx, Dy, Dz);
-  float lx = dot3_unfused(a.lo_view.px[0], a.lo_view.px[1], a.lo_view.px[2], Dx, Dy, Dz) / wq - a.lo_view.x0;
-  float ly = dot3_unfused(a.lo_view.py[0], a.lo_view.py[1], a.lo_view.py[2], Dx, Dy, Dz) / wq - a.lo_view.y0;
+  float D[3];
+  rp_centre_ray(a.rays, x, y, D);
+  float wq, lx, ly;
+  rp_project(a.lo_view, D[0], D[1], D[2], wq, lx, ly);
   lx = lx > 0.0f ? lx : 0.0f;  // (NaN too)
   lx = lx < a.xm ? lx : a.xm;
   ly = ly > 0.0f ? ly : 0.0f;
@@ -224,10 +222,7 @@ struct up_options {
   float plane_tol, normal_cos;
 };
 
-bool overlap(const void *p, size_t np, const void *q, size_t nq) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return p && q && a < b + nq && b < a + np;
-}
+using rtk::overlap;
 
 // false: an argument is NULL, out of range or NaN, the eyes differ, or the
 // buffers overlap.  scratch: the device entry point's (NULL: the synchronous
@@ -240,10 +235,9 @@ bool resolve(const rt_upscale_desc *d, const void *scratch, up_options &o) {
       !d->normal_hi || !d->out)
     return false;
   if (albedo && (!d->albedo_lo || !d->albedo_hi)) return false;
-  o.plane_tol = d->plane_tol == 0.0f ? rtk::kUpDefaultPlaneTol : d->plane_tol;
-  if (!(o.plane_tol > 0.0f)) return false;  // (NaN too)
-  o.normal_cos = d->normal_cos == 0.0f ? rtk::kUpDefaultNormalCos : d->normal_cos;
-  if (!(o.normal_cos >= -1.0f && o.normal_cos <= 1.0f)) return false;
+  if (!rtk::post_option(d->plane_tol, rtk::kUpDefaultPlaneTol, 0.0f, false, INFINITY, o.plane_tol) ||
+      !rtk::post_option(d->normal_cos, rtk::kUpDefaultNormalCos, -1.0f, true, 1.0f, o.normal_cos))
+    return false;
   if (std::memcmp(d->rays.eye, d->lo_view.eye, sizeof d->rays.eye) != 0) return false;
   const size_t nlo = (size_t)d->lo_width * (size_t)d->lo_height, nhi = (size_t)d->width * (size_t)d->height;
   // what the pass reads (the albedos only when it does), then what it writes
@@ -318,7 +312,7 @@ size_t rt_upscale_scratch_bytes(int lo_width, int lo_height) {
 
 int rt_upscale_async(rt_context *c, const rt_upscale_desc *d, void *scratch, void *stream) {
   up_options o;
-  if (!c || !d || !scratch || ((uintptr_t)scratch & 15) || !resolve(d, scratch, o)) return RT_ERR_INVALID;
+  if (!c || !d || !scratch || !rtk::post_aligned16(scratch) || !resolve(d, scratch, o)) return RT_ERR_INVALID;
   rt_pass_scope ps(c, nullptr, nullptr, stream);
   return ps.end(ps.status == RT_OK ? enqueue(d, o, scratch, ps.fs.stream) : ps.status);
 }

@@ -62,6 +62,7 @@ DENOISE_DEFAULTS = {"iterations": 5, "normal_power": 6, "sigma_plane": 0.5, "sig
 TEMPORAL_VERSION = 1  # include/rt_temporal.h RT_TEMPORAL_VERSION
 # rt_temporal_desc's pointers in order (history_in and out may be NULL), and its options with their defaults
 TEMPORAL_BUFFERS = ("cur", "hits", "position", "normal", "history_in", "history_out", "out")
+# (in the three *_DEFAULTS below the TYPE of a value is its desc field's: _pass_options converts with it)
 TEMPORAL_DEFAULTS = {"max_len": 2, "plane_tol": 0.0003, "normal_cos": 0.9}
 RESOLVE_VERSION = 1  # include/rt_resolve.h RT_RESOLVE_VERSION
 # rt_resolve_desc's pointers in order (history_in and out may be NULL), its options with their defaults, its flags
@@ -215,6 +216,18 @@ def _reject_unknown(names, known, what):
         raise ValueError(f"unknown {what} {unknown}")
 
 
+def _pass_options(options, defaults, what):
+    """The option fields of a pass's desc from a *_desc function's **options:
+    names outside `defaults` are rejected, None means left out, and 0 is
+    rejected, since the struct reads 0 as "default"; a field left out is 0."""
+    _reject_unknown(options, defaults, f"{what} options")
+    opt = {k: v for k, v in options.items() if v is not None}
+    zero = [k for k, v in opt.items() if v == 0]
+    if zero:
+        raise ValueError(f"{what} options {zero} must not be 0 (the struct's 0 means the default)")
+    return {k: type(dflt)(opt.get(k, 0)) for k, dflt in defaults.items()}  # (an int default: an int field)
+
+
 def _load_pass(path, version_fn, version, protos):
     """Load a pass's library (raises if it has not been built): librtow.so
     loads first, since the pass runs on its contexts; protos maps function
@@ -272,15 +285,7 @@ def temporal_desc(width, height, spp, prev_view=None, **options):
     or None take their defaults; a value means itself: plane_tol=inf and
     normal_cos=-1 switch their tests off.  The struct reads 0 as "default", so
     max_len=0, plane_tol=0 and normal_cos=0 cannot be asked for."""
-    _reject_unknown(options, TEMPORAL_DEFAULTS, "temporal options")
-    opt = {k: v for k, v in options.items() if v is not None}
-    zero = [k for k, v in opt.items() if v == 0]
-    if zero:
-        raise ValueError(f"temporal options {zero} must not be 0 (the struct's 0 means the default)")
-    d = TemporalDesc(width=width, height=height, spp=spp)
-    d.max_len = int(opt.get("max_len", 0))
-    d.plane_tol = float(opt.get("plane_tol", 0.0))
-    d.normal_cos = float(opt.get("normal_cos", 0.0))
+    d = TemporalDesc(width=width, height=height, spp=spp, **_pass_options(options, TEMPORAL_DEFAULTS, "temporal"))
     if prev_view is not None:
         d.prev = as_temporal_view(prev_view)
     return d
@@ -324,18 +329,10 @@ def resolve_desc(width, height, spp, prev_view=None, now_rays=None, flags=0, **o
     normal_cos=-1 and gamma=inf switch their steps off.  The struct reads 0 as
     "default", so an option of 0 cannot be asked for.  flags:
     RESOLVE_KEEP_PARTIAL or 0."""
-    _reject_unknown(options, RESOLVE_DEFAULTS, "resolve options")
-    opt = {k: v for k, v in options.items() if v is not None}
-    zero = [k for k, v in opt.items() if v == 0]
-    if zero:
-        raise ValueError(f"resolve options {zero} must not be 0 (the struct's 0 means the default)")
+    opt = _pass_options(options, RESOLVE_DEFAULTS, "resolve")
     if now_rays is None:
         raise ValueError("now_rays (resolve_rays of this frame's camera) is required")
-    d = ResolveDesc(width=width, height=height, spp=spp, flags=int(flags))
-    d.max_len = int(opt.get("max_len", 0))
-    d.plane_tol = float(opt.get("plane_tol", 0.0))
-    d.normal_cos = float(opt.get("normal_cos", 0.0))
-    d.gamma = float(opt.get("gamma", 0.0))
+    d = ResolveDesc(width=width, height=height, spp=spp, flags=int(flags), **opt)
     if prev_view is not None:
         d.prev = as_temporal_view(prev_view)
     d.now = as_resolve_rays(now_rays)
@@ -367,18 +364,12 @@ def upscale_desc(lo_width, lo_height, lo_spp, width, height, spp, lo_view=None, 
     an option of 0 cannot be asked for.  lo_view: temporal_view of the
     low-resolution camera; rays: resolve_rays of the output's camera (the two
     share the eye).  flags: UPSCALE_NO_ALBEDO or 0."""
-    _reject_unknown(options, UPSCALE_DEFAULTS, "upscale options")
-    opt = {k: v for k, v in options.items() if v is not None}
-    zero = [k for k, v in opt.items() if v == 0]
-    if zero:
-        raise ValueError(f"upscale options {zero} must not be 0 (the struct's 0 means the default)")
+    opt = _pass_options(options, UPSCALE_DEFAULTS, "upscale")
     if lo_view is None or rays is None:
         raise ValueError("lo_view (temporal_view of the low-resolution camera) and rays (resolve_rays of the "
                          "output's camera) are required")
     d = UpscaleDesc(lo_width=lo_width, lo_height=lo_height, lo_spp=lo_spp, width=width, height=height, spp=spp,
-                    flags=int(flags))
-    d.plane_tol = float(opt.get("plane_tol", 0.0))
-    d.normal_cos = float(opt.get("normal_cos", 0.0))
+                    flags=int(flags), **opt)
     d.lo_view = as_temporal_view(lo_view)
     d.rays = as_resolve_rays(rays)
     return d
@@ -854,16 +845,25 @@ class Context:
         None: no history).  Options: TEMPORAL_DEFAULTS (see temporal_desc).
         Returns (out, history_out): the accumulated sums (H, W, 3) and this
         frame's history; self.temporal_ms holds the launch's event time."""
+        return self._history_pass("temporal", temporal_lib, TEMPORAL_BUFFERS[1:4], cur, aov, history,
+                                  prev_view, lambda w, h: temporal_desc(w, h, spp, prev_view, **options))
+
+    def _history_pass(self, what, get_lib, inputs, cur, aov, history, prev_view, make_desc):
+        """What Context.temporal and Context.resolve share: the host arrays
+        (cur, the feature buffers `inputs` of aov, the history when there is
+        one) staged into make_desc(width, height), out and history_out
+        allocated, the call rt_<what> of get_lib() (loaded only after the
+        arguments passed) and self.<what>_ms."""
         if (history is None) != (prev_view is None):
             raise ValueError("history and prev_view go together")
-        d = temporal_desc(int(np.shape(cur)[1]), int(np.shape(cur)[0]), spp, prev_view, **options)
-        missing = [k for k in TEMPORAL_BUFFERS[1:4] if k not in aov]
+        d = make_desc(int(np.shape(cur)[1]), int(np.shape(cur)[0]))
+        missing = [k for k in inputs if k not in aov]
         if missing:
             raise ValueError(f"feature buffers {missing} are missing")
-        keep = {"cur": _frame_array("cur", cur, np.float32, d),
-                "hits": _frame_array("hits", aov["hits"], np.uint32, d, tail=())}
-        for k in TEMPORAL_BUFFERS[2:4]:
-            keep[k] = _frame_array(k, aov[k], np.float32, d)
+        keep = {"cur": _frame_array("cur", cur, np.float32, d)}
+        for k in inputs:
+            keep[k] = _frame_array(k, aov[k], np.uint32 if k == "hits" else np.float32, d,
+                                   tail=() if k in ("hits", "depth") else (3,))
         if history is not None:
             keep["history_in"] = _frame_array("history_in", history, np.float32, d, lead=(3,), tail=(4,))
         for k, a in keep.items():
@@ -872,8 +872,8 @@ class Context:
         history_out = np.zeros((3, d.height, d.width, 4), np.float32)
         d.out, d.history_out = out.ctypes.data, history_out.ctypes.data
         ms = ctypes.c_double()
-        check(temporal_lib().rt_temporal(self._h, ctypes.byref(d), ctypes.byref(ms)), "rt_temporal")
-        self.temporal_ms = ms.value
+        check(getattr(get_lib(), "rt_" + what)(self._h, ctypes.byref(d), ctypes.byref(ms)), "rt_" + what)
+        setattr(self, what + "_ms", ms.value)
         return out, history_out
 
     def temporal_async(self, dev_ptrs, width, height, spp, prev_view, stream=0, **options):
@@ -901,27 +901,9 @@ class Context:
         temporal_view (both None: no history).  Options: RESOLVE_DEFAULTS (see
         resolve_desc).  Returns (out, history_out) as Context.temporal;
         self.resolve_ms holds the launch's event time."""
-        if (history is None) != (prev_view is None):
-            raise ValueError("history and prev_view go together")
-        d = resolve_desc(int(np.shape(cur)[1]), int(np.shape(cur)[0]), spp, prev_view, now_rays, flags, **options)
-        missing = [k for k in RESOLVE_BUFFERS[1:4] if k not in aov]
-        if missing:
-            raise ValueError(f"feature buffers {missing} are missing")
-        keep = {"cur": _frame_array("cur", cur, np.float32, d),
-                "hits": _frame_array("hits", aov["hits"], np.uint32, d, tail=()),
-                "depth": _frame_array("depth", aov["depth"], np.float32, d, tail=()),
-                "normal": _frame_array("normal", aov["normal"], np.float32, d)}
-        if history is not None:
-            keep["history_in"] = _frame_array("history_in", history, np.float32, d, lead=(3,), tail=(4,))
-        for k, a in keep.items():
-            setattr(d, k, a.ctypes.data)
-        out = np.zeros((d.height, d.width, 3), np.float32)
-        history_out = np.zeros((3, d.height, d.width, 4), np.float32)
-        d.out, d.history_out = out.ctypes.data, history_out.ctypes.data
-        ms = ctypes.c_double()
-        check(resolve_lib().rt_resolve(self._h, ctypes.byref(d), ctypes.byref(ms)), "rt_resolve")
-        self.resolve_ms = ms.value
-        return out, history_out
+        return self._history_pass("resolve", resolve_lib, RESOLVE_BUFFERS[1:4], cur, aov, history,
+                                  prev_view,
+                                  lambda w, h: resolve_desc(w, h, spp, prev_view, now_rays, flags, **options))
 
     def resolve_async(self, dev_ptrs, width, height, spp, prev_view, now_rays, stream=0, flags=0, **options):
         """Enqueue the pass (rt_resolve_async) on raw device pointers (e.g.

@@ -1,6 +1,9 @@
 """What the numpy float32 restatements of the image-space passes
-(denoise_ref.py, temporal_ref.py) share, as the kernels share csrc/rt_post.h:
-the unfused dot product and the guide preparation from the rt_aov sums."""
+(denoise_ref.py, temporal_ref.py, resolve_ref.py, upscale_ref.py) share, as
+the kernels share csrc/rt_post.h: the unfused dot product and the guide
+preparation from the rt_aov sums.  What the passes that reproject share
+(csrc/rt_reproject.h) is temporal_ref.py's project, gather, blend and
+pack_history and resolve_ref.py's centre_rays."""
 import numpy as np
 
 F = np.float32

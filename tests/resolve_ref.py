@@ -5,8 +5,9 @@ nine neighbourhood pixels and the four taps in the specified order.  Every
 intermediate is a float32 array, so each numpy operation rounds once, like the
 kernel's (no contraction there): the two agree bit for bit.
 
-The projection is temporal_ref's (rt_temporal.h's "View"); the guide
-preparation is post_ref's.  The options are the EFFECTIVE ones (after the
+The projection, the gather, the blend and the history packing are
+temporal_ref's (csrc/rt_reproject.h on the device); the guide preparation is
+post_ref's.  The options are the EFFECTIVE ones (after the
 desc's "0 = default" rule): plane_tol inf = plane test off, normal_cos -1 =
 normal test off, gamma inf = clamp off."""
 from collections import namedtuple
@@ -99,78 +100,31 @@ def resolve_ref(cur, hits, depth, normal, spp, rays, prev=None, history=None, ma
     if census is not None:
         census.clear()
     if history is not None:
-        history = np.asarray(history, F)
-        assert history.shape == (3, H, W, 4)
         partial = ~sky & (hits < np.uint32(spp))
         use = ~sky & (~partial if not flags & KEEP_PARTIAL else True)
         # 4. reproject and gather: rt_temporal.h's steps 3 and 4 with this P and n
-        q, w, x, y = tref.project(prev, P)
-        ok = use & (w > 0) & (x > F(-1)) & (x < F(W)) & (y > F(-1)) & (y < F(H))
-        xs, ys = np.where(ok, x, F(0)), np.where(ok, y, F(0))  # (the rest is never used)
-        xf, yf = np.floor(xs), np.floor(ys)
-        fx, fy = xs - xf, ys - yf
-        xi, yi = xf.astype(np.int64), yf.astype(np.int64)
-        d2 = _dot(q, q)
-        pt2 = F(plane_tol) * F(plane_tol)
-        with np.errstate(invalid="ignore", over="ignore"):
-            lim = pt2 * d2
-        sw, sl, sc = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W, 3), F)
-        taken = np.zeros((H, W), np.int64)
-        count = dict(off_frame=0, sky_tap=0, plane=0, normal=0)
-        for dy in (0, 1):
-            for dx in (0, 1):
-                tx, ty = xi + dx, yi + dy
-                inside = ok & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
-                txc, tyc = np.clip(tx, 0, W - 1), np.clip(ty, 0, H - 1)
-                rgbl, Pt, nt = history[0, tyc, txc], history[1, tyc, txc], history[2, tyc, txc]
-                geo = inside & (Pt[..., 3] == 0)
-                with np.errstate(invalid="ignore", over="ignore"):
-                    e = _dot(n, Pt[..., :3] - P)
-                    plane = (e * e <= lim) if np.isfinite(plane_tol) else np.ones((H, W), bool)
-                    g = _dot(n, nt[..., :3])
-                same = (g >= F(normal_cos)) if normal_cos != -1 else np.ones((H, W), bool)
-                take = geo & plane & same
-                b = (fx if dx else F(1) - fx) * (fy if dy else F(1) - fy)
-                assert b.dtype == F
-                with np.errstate(invalid="ignore", over="ignore"):
-                    sw = np.where(take, sw + b, sw)
-                    sc = np.where(take[..., None], sc + b[..., None] * rgbl[..., :3], sc)
-                    sl = np.where(take, sl + b * rgbl[..., 3], sl)
-                taken += take
-                count["off_frame"] += int((ok & ~inside).sum())
-                count["sky_tap"] += int((inside & ~geo).sum())
-                count["plane"] += int((geo & ~plane).sum())
-                count["normal"] += int((geo & plane & ~same).sum())
-        # 5. blend
+        sw, sc, sl, ok, did = tref.gather(history, prev, P, n, use, plane_tol, normal_cos)
+        # 5. clamp and blend
         valid = ok & (sw > 0)
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
             raw = sc / sw[..., None]
-            hl = sl / sw
             hist = raw
             if np.isfinite(gamma):
                 lo, hi, k = neighbourhood(c, gamma)
                 hist = np.where(raw < lo, lo, np.where(raw > hi, hi, raw))
-            t = hl + F(1)
-            lv = np.where(t < F(max_len), t, F(max_len)).astype(F)
-            a = F(1) / lv
-            mv = hist + (c - hist) * a[..., None]
-        assert mv.dtype == F and lv.dtype == F and hist.dtype == F
+            mv, lv, t = tref.blend(c, hist, sl / sw, max_len)
+        assert hist.dtype == F
         m = np.where(valid[..., None], mv, c)
         ln = np.where(valid, lv, F(1)).astype(F)
         if census is not None:
-            census.update(count, ok=ok, valid=valid, taken=taken, w=w, x=x, y=y, xi=xi, yi=yi, use=use,
-                          partial=partial, saturated=valid & (t >= F(max_len)), hist=hist)
+            census.update(did, valid=valid, use=use, partial=partial, saturated=valid & (t >= F(max_len)), hist=hist)
             if np.isfinite(gamma):
                 v3 = valid[..., None]
                 census.update(lo=lo, hi=hi, k=k, clamp_low=v3 & (raw < lo), clamp_high=v3 & ~(raw < lo) & (raw > hi),
                               clamp_idle=v3 & ~(raw < lo) & ~(raw > hi))
     out = m * F(spp)
-    hout = np.zeros((3, H, W, 4), F)
-    hout[0, ..., :3], hout[0, ..., 3] = m, ln
-    hout[1, ..., :3], hout[1, ..., 3] = P, sky
-    hout[2, ..., :3] = n
     assert out.dtype == F
-    return out, hout
+    return out, tref.pack_history(m, ln, P, sky, n)
 
 
 def identity_inputs(w, h, spp, colour, hits=None):

@@ -24,15 +24,22 @@ def _v3(v):
     return np.array([v[0], v[1], v[2]], F)
 
 
-def project(view, P):
-    """The header's "View" in float32: P (..., 3) -> (q, w, x, y)."""
-    q = np.asarray(P, F) - _v3(view.eye)
+def project_rel(view, q):
+    """The header's "View" in float32 for vectors relative to the eye: q
+    (..., 3) -> (w, x, y)."""
+    q = np.asarray(q, F)
     w = _dot(_v3(view.pw), q)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         x = _dot(_v3(view.px), q) / w - F(view.x0)
         y = _dot(_v3(view.py), q) / w - F(view.y0)
     assert q.dtype == w.dtype == x.dtype == y.dtype == F
-    return q, w, x, y
+    return w, x, y
+
+
+def project(view, P):
+    """The same for points: P (..., 3) -> (q, w, x, y) with q = P - eye."""
+    q = np.asarray(P, F) - _v3(view.eye)
+    return (q,) + project_rel(view, q)
 
 
 def prepare(cur, hits, position, normal, spp):
@@ -44,6 +51,77 @@ def prepare(cur, hits, position, normal, spp):
     return c.astype(F), n, P, sky
 
 
+def gather(history, prev, P, n, use, plane_tol, normal_cos):
+    """Steps 3 and 4 for the pixels of the mask `use`: P (H, W, 3) projected
+    through prev and the four taps around it, dy outer, dx inner -> (sw (H, W),
+    sc (H, W, 3), sl (H, W), ok, census): the bilinear sums of the taps on the
+    pixel's surface, the pixels whose projection lies on the frame, and what
+    the pixels and their taps did (masks and counts)."""
+    history = np.asarray(history, F)
+    H, W = use.shape
+    assert history.shape == (3, H, W, 4)
+    q, w, x, y = project(prev, P)
+    ok = use & (w > 0) & (x > F(-1)) & (x < F(W)) & (y > F(-1)) & (y < F(H))
+    xs, ys = np.where(ok, x, F(0)), np.where(ok, y, F(0))  # (the rest is never used)
+    xf, yf = np.floor(xs), np.floor(ys)
+    fx, fy = xs - xf, ys - yf
+    xi, yi = xf.astype(np.int64), yf.astype(np.int64)
+    d2 = _dot(q, q)
+    pt2 = F(plane_tol) * F(plane_tol)
+    with np.errstate(invalid="ignore", over="ignore"):
+        lim = pt2 * d2
+    sw, sl, sc = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W, 3), F)
+    taken = np.zeros((H, W), np.int64)
+    count = dict(off_frame=0, sky_tap=0, plane=0, normal=0)
+    for dy in (0, 1):
+        for dx in (0, 1):
+            tx, ty = xi + dx, yi + dy
+            inside = ok & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
+            txc, tyc = np.clip(tx, 0, W - 1), np.clip(ty, 0, H - 1)
+            rgbl, Pt, nt = history[0, tyc, txc], history[1, tyc, txc], history[2, tyc, txc]
+            geo = inside & (Pt[..., 3] == 0)
+            with np.errstate(invalid="ignore", over="ignore"):
+                e = _dot(n, Pt[..., :3] - P)
+                plane = (e * e <= lim) if np.isfinite(plane_tol) else np.ones((H, W), bool)
+                g = _dot(n, nt[..., :3])
+            same = (g >= F(normal_cos)) if normal_cos != -1 else np.ones((H, W), bool)
+            take = geo & plane & same
+            b = (fx if dx else F(1) - fx) * (fy if dy else F(1) - fy)
+            assert b.dtype == F
+            with np.errstate(invalid="ignore", over="ignore"):
+                sw = np.where(take, sw + b, sw)
+                sc = np.where(take[..., None], sc + b[..., None] * rgbl[..., :3], sc)
+                sl = np.where(take, sl + b * rgbl[..., 3], sl)
+            taken += take
+            count["off_frame"] += int((ok & ~inside).sum())
+            count["sky_tap"] += int((inside & ~geo).sum())
+            count["plane"] += int((geo & ~plane).sum())
+            count["normal"] += int((geo & plane & ~same).sum())
+    return sw, sc, sl, ok, dict(count, ok=ok, taken=taken, w=w, x=x, y=y, xi=xi, yi=yi)
+
+
+def blend(c, hist, hl, max_len):
+    """Step 5 -> (mv, lv, t): the history's mean colour hist (clamped by the
+    caller where it clamps) and length hl blended with the new colour c, the new
+    length, and the length before its cap."""
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        t = hl + F(1)
+        lv = np.where(t < F(max_len), t, F(max_len)).astype(F)
+        a = F(1) / lv
+        mv = hist + (c - hist) * a[..., None]
+    assert mv.dtype == F and lv.dtype == F
+    return mv, lv, t
+
+
+def pack_history(m, ln, P, sky, n):
+    """Step 6 -> history_out (3, H, W, 4)."""
+    hout = np.zeros((3,) + sky.shape + (4,), F)
+    hout[0, ..., :3], hout[0, ..., 3] = m, ln
+    hout[1, ..., :3], hout[1, ..., 3] = P, sky
+    hout[2, ..., :3] = n
+    return hout
+
+
 def temporal_ref(cur, hits, position, normal, spp, prev=None, history=None, max_len=2, plane_tol=0.0003,
                  normal_cos=0.9, census=None):
     """cur, position, normal (H, W, 3) float32 sums, hits (H, W) uint32, history
@@ -52,72 +130,22 @@ def temporal_ref(cur, hits, position, normal, spp, prev=None, history=None, max_
     their taps did: masks and counts for the tests that ask whether their
     inputs reach every branch."""
     c, n, P, sky = prepare(cur, hits, position, normal, spp)
-    H, W = sky.shape
     m = c.copy()
-    ln = np.ones((H, W), F)
+    ln = np.ones(sky.shape, F)
     if census is not None:
         census.clear()
     if history is not None:
-        history = np.asarray(history, F)
-        assert history.shape == (3, H, W, 4)
-        q, w, x, y = project(prev, P)
-        ok = ~sky & (w > 0) & (x > F(-1)) & (x < F(W)) & (y > F(-1)) & (y < F(H))
-        xs, ys = np.where(ok, x, F(0)), np.where(ok, y, F(0))  # (the rest is never used)
-        xf, yf = np.floor(xs), np.floor(ys)
-        fx, fy = xs - xf, ys - yf
-        xi, yi = xf.astype(np.int64), yf.astype(np.int64)
-        d2 = _dot(q, q)
-        pt2 = F(plane_tol) * F(plane_tol)
-        with np.errstate(invalid="ignore", over="ignore"):
-            lim = pt2 * d2
-        sw, sl, sc = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W, 3), F)
-        taken = np.zeros((H, W), np.int64)
-        count = dict(off_frame=0, sky_tap=0, plane=0, normal=0)
-        for dy in (0, 1):
-            for dx in (0, 1):
-                tx, ty = xi + dx, yi + dy
-                inside = ok & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
-                txc, tyc = np.clip(tx, 0, W - 1), np.clip(ty, 0, H - 1)
-                rgbl, Pt, nt = history[0, tyc, txc], history[1, tyc, txc], history[2, tyc, txc]
-                geo = inside & (Pt[..., 3] == 0)
-                with np.errstate(invalid="ignore", over="ignore"):
-                    e = _dot(n, Pt[..., :3] - P)
-                    plane = (e * e <= lim) if np.isfinite(plane_tol) else np.ones((H, W), bool)
-                    g = _dot(n, nt[..., :3])
-                same = (g >= F(normal_cos)) if normal_cos != -1 else np.ones((H, W), bool)
-                use = geo & plane & same
-                b = (fx if dx else F(1) - fx) * (fy if dy else F(1) - fy)
-                assert b.dtype == F
-                with np.errstate(invalid="ignore", over="ignore"):
-                    sw = np.where(use, sw + b, sw)
-                    sc = np.where(use[..., None], sc + b[..., None] * rgbl[..., :3], sc)
-                    sl = np.where(use, sl + b * rgbl[..., 3], sl)
-                taken += use
-                count["off_frame"] += int((ok & ~inside).sum())
-                count["sky_tap"] += int((inside & ~geo).sum())
-                count["plane"] += int((geo & ~plane).sum())
-                count["normal"] += int((geo & plane & ~same).sum())
+        sw, sc, sl, ok, did = gather(history, prev, P, n, ~sky, plane_tol, normal_cos)
         valid = ok & (sw > 0)
         with np.errstate(divide="ignore", invalid="ignore"):
-            hist = sc / sw[..., None]
-            hl = sl / sw
-            t = hl + F(1)
-            lv = np.where(t < F(max_len), t, F(max_len)).astype(F)
-            a = F(1) / lv
-            mv = hist + (c - hist) * a[..., None]
-        assert mv.dtype == F and lv.dtype == F
+            mv, lv, t = blend(c, sc / sw[..., None], sl / sw, max_len)
         m = np.where(valid[..., None], mv, c)
         ln = np.where(valid, lv, F(1)).astype(F)
         if census is not None:
-            census.update(count, ok=ok, valid=valid, taken=taken, w=w, x=x, y=y, xi=xi, yi=yi,
-                          saturated=valid & (t >= F(max_len)))
+            census.update(did, valid=valid, saturated=valid & (t >= F(max_len)))
     out = m * F(spp)
-    hout = np.zeros((3, H, W, 4), F)
-    hout[0, ..., :3], hout[0, ..., 3] = m, ln
-    hout[1, ..., :3], hout[1, ..., 3] = P, sky
-    hout[2, ..., :3] = n
     assert out.dtype == F
-    return out, hout
+    return out, pack_history(m, ln, P, sky, n)
 
 
 def orbit(lookfrom, lookat, degrees):

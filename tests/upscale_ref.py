@@ -5,9 +5,9 @@ intermediate is a float32 array, so each numpy operation rounds once, like the
 kernels' (no contraction there): the two agree bit for bit.
 
 The guide preparation is post_ref's, the demodulation denoise_ref's, the rays
-resolve_ref's.  The options are the EFFECTIVE ones (after the desc's "0 =
-default" rule): plane_tol inf = plane test off, normal_cos -1 = normal test
-off."""
+resolve_ref's, the projection temporal_ref's.  The options are the EFFECTIVE
+ones (after the desc's "0 = default" rule): plane_tol inf = plane test off,
+normal_cos -1 = normal test off."""
 import numpy as np
 
 import temporal_ref as tref
@@ -47,10 +47,8 @@ def map_pixels(lo_view, rays, w, h, W, H):
     """Step 2 -> (xi, yi, fx, fy, x_raw, y_raw): where the output's pixels lie
     in the low-resolution frame."""
     D = centre_rays(rays, W, H)
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        wq = _dot(_v3(lo_view.pw), D)
-        xr = _dot(_v3(lo_view.px), D) / wq - F(lo_view.x0)
-        yr = _dot(_v3(lo_view.py), D) / wq - F(lo_view.y0)
+    _, xr, yr = tref.project_rel(lo_view, D)
+    with np.errstate(invalid="ignore"):
         x = np.where(xr > 0, xr, F(0))
         x = np.where(x < F(w - 1), x, F(w - 1))
         y = np.where(yr > 0, yr, F(0))

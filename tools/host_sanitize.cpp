@@ -2,7 +2,8 @@
 // on the CPU (no device): the scene builders, both cameras, the BVH / layer-grid
 // builder (rt_internal_accel_info) and its grid fitter (csrc/rt_accel.h, linked
 // directly), both tonemaps and the P3 / P6 writers, on the reference scenes
-// and on ragged / degenerate inputs.  Built and run by
+// and on ragged / degenerate inputs, and the argument rules the image-space
+// passes share (csrc/rt_post.h, csrc/rt_reproject.h: inline, no device).  Built and run by
 // tools/host_sanitize.sh; exits non-zero on any failed check (the sanitizers
 // abort on their own findings).
 #include <cmath>
@@ -15,6 +16,7 @@
 
 #include "rt_internal.h"
 #include "rt_accel.h"
+#include "rt_reproject.h"
 
 #define CHECK(x)                                                    \
   do {                                                              \
@@ -197,6 +199,33 @@ int main() {
         CHECK(plan[0] <= plan[3] && (spp == 0 || plan[1] <= (uint64_t)spp));
       }
     }
+  }
+  // the passes' shared argument rules (csrc/rt_post.h, csrc/rt_reproject.h)
+  {
+    char buf[64];
+    CHECK(rtk::overlap(buf, 16, buf + 15, 16) && rtk::overlap(buf + 15, 16, buf, 16) && rtk::overlap(buf, 64, buf, 1));
+    CHECK(!rtk::overlap(buf, 16, buf + 16, 16) && !rtk::overlap(buf + 16, 16, buf, 16));
+    CHECK(!rtk::overlap(nullptr, 16, buf, 16) && !rtk::overlap(buf, 16, nullptr, 16));
+    CHECK(rtk::post_aligned16(nullptr) && rtk::post_aligned16((void *)(uintptr_t)32) &&
+          !rtk::post_aligned16((void *)(uintptr_t)40));
+    int n = -1;
+    CHECK(rtk::post_option(0, 2, 1, true, 1024, n) && n == 2);
+    CHECK(rtk::post_option(1024, 2, 1, true, 1024, n) && n == 1024);
+    CHECK(!rtk::post_option(1025, 2, 1, true, 1024, n) && !rtk::post_option(-1, 2, 1, true, 1024, n));
+    float v = -1.0f;
+    CHECK(rtk::post_option(0.0f, 0.5f, 0.0f, false, INFINITY, v) && v == 0.5f);
+    CHECK(rtk::post_option(-0.0f, 0.5f, 0.0f, false, INFINITY, v) && v == 0.5f);
+    CHECK(rtk::post_option(INFINITY, 0.5f, 0.0f, false, INFINITY, v) && std::isinf(v));
+    CHECK(!rtk::post_option(-1e-30f, 0.5f, 0.0f, false, INFINITY, v) && !rtk::post_option(NAN, 0.5f, 0.0f, false, INFINITY, v));
+    CHECK(rtk::post_option(-1.0f, 0.9f, -1.0f, true, 1.0f, v) && v == -1.0f);
+    CHECK(!rtk::post_option(1.5f, 0.9f, -1.0f, true, 1.0f, v) && !rtk::post_option(NAN, 0.9f, -1.0f, true, 1.0f, v));
+    CHECK(rtk::rp_camera_ok(&cam, 1, 1) && !rtk::rp_camera_ok(nullptr, 4, 4) && !rtk::rp_camera_ok(&cam, 0, 4) &&
+          !rtk::rp_camera_ok(&cam, 4, 32769));
+    rt_camera cpu_cam;
+    CHECK(rt_camera_cpu(from, at, up, 20.0, 16.0 / 9.0, 0.1, 10.0, &cpu_cam) == RT_OK);
+    CHECK(rtk::rp_camera_ok(&cpu_cam, 2, 2) && !rtk::rp_camera_ok(&cpu_cam, 1, 2) && !rtk::rp_camera_ok(&cpu_cam, 2, 1));
+    cpu_cam.model = 77;
+    CHECK(!rtk::rp_camera_ok(&cpu_cam, 4, 4));
   }
   std::printf("host_sanitize: ok\n");
   return 0;
