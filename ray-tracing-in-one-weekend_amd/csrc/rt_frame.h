@@ -8,10 +8,13 @@
 // librtow_temporal.so, the resolve in rt_resolve.hip / librtow_resolve.so,
 // upsampling in rt_upscale.hip / librtow_upscale.so) with
 // rt_internal_pass_begin; what those share beyond this header is in rt_post.h
-// and rt_reproject.h.  The helpers: hip_fail /
-// RT_HIP, rt_pass_scope, rt_device_buf and rt_sync_pass, the one
-// host sequence of the synchronous rt_aov / rt_denoise / rt_temporal /
-// rt_resolve / rt_upscale / rt_guides.  Not
+// and rt_reproject.h, and what the two traced feature passes share (device
+// and host) in rt_trace_pass.h.  The helpers: hip_fail /
+// RT_HIP, the traced passes' cut of a frame's samples into launches
+// (rt_samples_per_launch, rt_sample_ranges: no HIP in them, so that
+// tools/host_sanitize.cpp checks them), rt_pass_scope, rt_device_buf and
+// rt_sync_pass, the one host sequence of the synchronous rt_aov / rt_denoise /
+// rt_temporal / rt_resolve / rt_upscale / rt_guides.  Not
 // installed; rt_context stays opaque outside rt_api.cpp, so the other
 // libraries get what they need through rt_frame_setup.
 #ifndef RTOW_RT_FRAME_H
@@ -19,6 +22,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 #include <utility>
@@ -82,6 +87,25 @@ inline long long rt_frame_tiles(const rt_params *prm) {
 }
 inline long long rt_frame_blocks(const rt_params *prm) {
   return (rt_frame_tiles(prm) + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock;
+}
+
+// How a traced feature pass (rt_trace_pass.h) cuts a frame's spp samples per
+// pixel into launches: `per` samples of every pixel per launch, about
+// launch_samples (RT_OPT_LAUNCH_SAMPLES) samples of the frame_px pixels at
+// most, at least one; at most kMaxLaunches launches.  No HIP in either.
+inline long long rt_samples_per_launch(int spp, double frame_px, double launch_samples) {
+  const long long per = (long long)std::min((double)std::max(spp, 1), std::floor(launch_samples / frame_px));
+  return std::max({per, 1LL, ((long long)spp + rtk::kMaxLaunches - 1) / rtk::kMaxLaunches});
+}
+// f(s_lo, s_cnt) for the ranges in ascending order, until one fails.  spp = 0:
+// one range (0, 0), a launch that only initialises.
+template <class F>
+int rt_sample_ranges(int spp, long long per, F f) {
+  for (long long s0 = 0; s0 == 0 || s0 < spp; s0 += per) {
+    const int r = f((int)s0, (int)std::min<long long>(per, spp - s0));
+    if (r != RT_OK) return r;
+  }
+  return RT_OK;
 }
 
 // One pass on a stream: begins it (cam NULL: rt_internal_pass_begin, else

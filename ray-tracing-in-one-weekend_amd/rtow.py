@@ -737,35 +737,43 @@ class Context:
                                     ctypes.c_void_p(dev_ptr), ctypes.c_void_p(stream)),
               "rt_render_async")
 
+    def _feature_pass(self, fields, buffers_type, call, name, cam, params, which, opts=()):
+        """Context.aov / Context.guides: the wanted host arrays, the call, the dict."""
+        _reject_unknown(which, [f[0] for f in fields], "feature buffers")
+        out, bufs = {}, buffers_type()
+        for field, dt, ch in fields:
+            if field in which:
+                shape = (params.local_rows, params.width) + ((3,) if ch == 3 else ())
+                out[field] = np.zeros(shape, dt)
+                setattr(bufs, field, out[field].ctypes.data)
+        ms = ctypes.c_double()
+        check(call(self._h, ctypes.byref(cam), ctypes.byref(params), *opts, ctypes.byref(bufs), ctypes.byref(ms)), name)
+        out["kernel_ms"] = ms.value
+        return out
+
+    def _feature_pass_async(self, fields, buffers_type, call, name, cam, params, dev_ptrs, stream, opts=()):
+        """Context.aov_async / Context.guides_async: the device pointers, the call."""
+        _reject_unknown(dev_ptrs, [f[0] for f in fields], "feature buffers")
+        bufs = buffers_type()
+        for field, ptr in dev_ptrs.items():
+            setattr(bufs, field, ptr)
+        check(call(self._h, ctypes.byref(cam), ctypes.byref(params), *opts, ctypes.byref(bufs),
+                   ctypes.c_void_p(stream)), name)
+
     def aov(self, cam, params, which=("hits", "id", "depth", "position", "normal", "albedo")):
         """First-hit feature buffers of the render's primary rays (rt_aov,
         include/rt_aov.h), synchronously: a dict of numpy arrays shaped
         (local_rows, W) or (local_rows, W, 3) for the names in `which`, holding
         unnormalised sums over each pixel's hit samples (divide by "hits"), plus
         "kernel_ms"."""
-        _reject_unknown(which, [f[0] for f in AOV_FIELDS], "feature buffers")
-        out, bufs = {}, AovBuffers()
-        for name, dt, ch in AOV_FIELDS:
-            if name in which:
-                shape = (params.local_rows, params.width) + ((3,) if ch == 3 else ())
-                out[name] = np.zeros(shape, dt)
-                setattr(bufs, name, out[name].ctypes.data)
-        ms = ctypes.c_double()
-        check(aov_lib().rt_aov(self._h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(bufs),
-                               ctypes.byref(ms)), "rt_aov")
-        out["kernel_ms"] = ms.value
-        return out
+        return self._feature_pass(AOV_FIELDS, AovBuffers, aov_lib().rt_aov, "rt_aov", cam, params, which)
 
     def aov_async(self, cam, params, dev_ptrs, stream=0):
         """Enqueue the first-hit pass (rt_aov_async) into raw device pointers
         (e.g. torch tensor.data_ptr()): dev_ptrs maps names of AOV_FIELDS to
         device pointers; names left out are not computed."""
-        _reject_unknown(dev_ptrs, [f[0] for f in AOV_FIELDS], "feature buffers")
-        bufs = AovBuffers()
-        for name, ptr in dev_ptrs.items():
-            setattr(bufs, name, ptr)
-        check(aov_lib().rt_aov_async(self._h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(bufs),
-                                     ctypes.c_void_p(stream)), "rt_aov_async")
+        self._feature_pass_async(AOV_FIELDS, AovBuffers, aov_lib().rt_aov_async, "rt_aov_async", cam, params,
+                                 dev_ptrs, stream)
 
     def guides(self, cam, params, which=tuple(f[0] for f in GUIDES_FIELDS), max_bounces=None, max_fuzz=None):
         """Feature buffers that follow each sample's path through mirrors and
@@ -775,17 +783,8 @@ class Context:
         plus "bounces" and "escaped".  Options: see guides_options."""
         _reject_unknown(which, [f[0] for f in GUIDES_FIELDS], "feature buffers")
         opts = guides_options(max_bounces, max_fuzz)
-        out, bufs = {}, GuidesBuffers()
-        for name, dt, ch in GUIDES_FIELDS:
-            if name in which:
-                shape = (params.local_rows, params.width) + ((3,) if ch == 3 else ())
-                out[name] = np.zeros(shape, dt)
-                setattr(bufs, name, out[name].ctypes.data)
-        ms = ctypes.c_double()
-        check(guides_lib().rt_guides(self._h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(opts),
-                                     ctypes.byref(bufs), ctypes.byref(ms)), "rt_guides")
-        out["kernel_ms"] = ms.value
-        return out
+        return self._feature_pass(GUIDES_FIELDS, GuidesBuffers, guides_lib().rt_guides, "rt_guides", cam, params,
+                                  which, (ctypes.byref(opts),))
 
     def guides_async(self, cam, params, dev_ptrs, stream=0, max_bounces=None, max_fuzz=None):
         """Enqueue the pass (rt_guides_async) into raw device pointers (e.g.
@@ -793,11 +792,8 @@ class Context:
         pointers; names left out are not computed."""
         _reject_unknown(dev_ptrs, [f[0] for f in GUIDES_FIELDS], "feature buffers")
         opts = guides_options(max_bounces, max_fuzz)
-        bufs = GuidesBuffers()
-        for name, ptr in dev_ptrs.items():
-            setattr(bufs, name, ptr)
-        check(guides_lib().rt_guides_async(self._h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(opts),
-                                           ctypes.byref(bufs), ctypes.c_void_p(stream)), "rt_guides_async")
+        self._feature_pass_async(GUIDES_FIELDS, GuidesBuffers, guides_lib().rt_guides_async, "rt_guides_async", cam,
+                                 params, dev_ptrs, stream, (ctypes.byref(opts),))
 
     def denoise(self, beauty, aov, spp, **options):
         """The guided a-trous filter (rt_denoise, include/rt_denoise.h),

@@ -3,7 +3,8 @@
 // builder (rt_internal_accel_info) and its grid fitter (csrc/rt_accel.h, linked
 // directly), both tonemaps and the P3 / P6 writers, on the reference scenes
 // and on ragged / degenerate inputs, and the argument rules the image-space
-// passes share (csrc/rt_post.h, csrc/rt_reproject.h: inline, no device).  Built and run by
+// passes share (csrc/rt_post.h, csrc/rt_reproject.h: inline, no device), and the
+// traced passes' sample cut (csrc/rt_frame.h).  Built and run by
 // tools/host_sanitize.sh; exits non-zero on any failed check (the sanitizers
 // abort on their own findings).
 #include <cmath>
@@ -16,6 +17,7 @@
 
 #include "rt_internal.h"
 #include "rt_accel.h"
+#include "rt_frame.h"
 #include "rt_reproject.h"
 
 #define CHECK(x)                                                    \
@@ -226,6 +228,45 @@ int main() {
     CHECK(rtk::rp_camera_ok(&cpu_cam, 2, 2) && !rtk::rp_camera_ok(&cpu_cam, 1, 2) && !rtk::rp_camera_ok(&cpu_cam, 2, 1));
     cpu_cam.model = 77;
     CHECK(!rtk::rp_camera_ok(&cpu_cam, 4, 4));
+  }
+  // the traced feature passes' cut of a frame's samples into launches (csrc/rt_frame.h)
+  {
+    struct range {
+      int lo, cnt;
+    };
+    const auto ranges = [](int spp, double frame_px, double launch_samples) {
+      std::vector<range> r;
+      const long long per = rt_samples_per_launch(spp, frame_px, launch_samples);
+      CHECK(per >= 1);
+      CHECK(rt_sample_ranges(spp, per, [&](int lo, int cnt) {
+              r.push_back({lo, cnt});
+              return (int)RT_OK;
+            }) == RT_OK);
+      return r;
+    };
+    std::vector<range> r = ranges(0, 64.0 * 64.0, 1e6);  // spp = 0: one launch that only initialises
+    CHECK(r.size() == 1 && r[0].lo == 0 && r[0].cnt == 0);
+    r = ranges(1, 64.0 * 64.0, 1e6);
+    CHECK(r.size() == 1 && r[0].lo == 0 && r[0].cnt == 1);
+    CHECK(rt_samples_per_launch(16, 3840.0 * 2160.0, 1e6) == 1);  // a frame larger than launch_samples
+    CHECK(ranges(16, 3840.0 * 2160.0, 1e6).size() == 16);
+    CHECK(rt_samples_per_launch(16, 64.0 * 64.0, 1e6) == 16 && rt_samples_per_launch(500, 64.0 * 64.0, 1e6) == 244);
+    for (int spp : {1, 7, 500, 65536, 65537, 200000, (1 << 24) - 1})
+      for (double frame_px : {1.0, 64.0 * 64.0, 16384.0 * 16384.0})
+        for (double budget : {1.0, 1e6, 1099511627776.0}) {
+          r = ranges(spp, frame_px, budget);
+          CHECK(!r.empty() && r.size() <= (size_t)rtk::kMaxLaunches);
+          long long next = 0;
+          for (const range &x : r) {  // ascending, contiguous, none empty
+            CHECK(x.lo == next && x.cnt >= 1);
+            next += x.cnt;
+          }
+          CHECK(next == spp);
+        }
+    // a failing launch ends the ranges with its status
+    int calls = 0;
+    CHECK(rt_sample_ranges(8, 2, [&](int, int) { return ++calls == 2 ? (int)RT_ERR_HIP : (int)RT_OK; }) == RT_ERR_HIP &&
+          calls == 2);
   }
   std::printf("host_sanitize: ok\n");
   return 0;
