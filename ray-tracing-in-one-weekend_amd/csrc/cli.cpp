@@ -15,7 +15,7 @@
 //   extent; 11 = reference, 50 = 10k spheres) --scene final|five
 //   --camera cpu|gpu --semantics cpu|gpu --accel bvh|scan --gpus N --device N
 //   --devices D0,D1,... --gather rccl|host --out FILE --p6 --quiet
-//   --denoise[=ITERATIONS] --denoise-guides=first|chain
+//   --denoise[=ITERATIONS] --denoise-guides=first|chain|route
 // With --gpus N > 1 the frame is split into interleaved 8-row bands, one
 // context and stream per device; each device tonemaps its tile to bytes
 // (rt_tonemap_async) and the byte tiles are gathered to device 0 with one
@@ -31,7 +31,9 @@
 // same stream; write_color and the PPM path then run on the filtered sums.
 // --denoise-guides=chain (with --denoise only) guides the filter with rt_guides
 // at its defaults (rt_guides.h: the buffers follow mirror and glass paths)
-// instead of rt_aov; first, the default, is rt_aov.
+// instead of rt_aov, =route with rt_route at its defaults (rt_route.h: the
+// buffers of each pixel's dominant specular route); first, the default, is
+// rt_aov.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -52,6 +54,7 @@
 #include "rt_aov.h"
 #include "rt_denoise.h"
 #include "rt_guides.h"
+#include "rt_route.h"
 
 namespace {
 
@@ -72,7 +75,7 @@ struct options {
   double launch_samples = 0.0;  // RT_OPT_LAUNCH_SAMPLES (0: the library's default)
   bool denoise = false;
   int denoise_iterations = 0;  // --denoise=N (0: the library's default)
-  bool guides_set = false, guides_chain = false;  // --denoise-guides=first|chain
+  bool guides_set = false, guides_chain = false, guides_route = false;  // --denoise-guides=first|chain|route
 };
 
 [[noreturn]] void die(const char *what, int st) {
@@ -90,7 +93,7 @@ void check(int st, const char *what) {
                "          [--spheres HALF_EXTENT] [--scene final|five] [--camera cpu|gpu]\n"
                "          [--semantics cpu|gpu] [--accel bvh|scan] [--gpus N] [--device N]\n"
                "          [--devices D0,D1,...] [--gather rccl|host] [--out FILE] [--p6] [--quiet]\n"
-               "          [--launch-samples N] [--denoise[=ITERATIONS]] [--denoise-guides=first|chain]\n",
+               "          [--launch-samples N] [--denoise[=ITERATIONS]] [--denoise-guides=first|chain|route]\n",
                argv0);
   std::exit(2);
 }
@@ -151,9 +154,10 @@ int main(int argc, char **argv) {
     else if (a == "--denoise") o.denoise = true;
     else if (a.rfind("--denoise-guides=", 0) == 0) {
       const std::string v = a.substr(17);
-      if (v != "first" && v != "chain") usage(argv[0]);
+      if (v != "first" && v != "chain" && v != "route") usage(argv[0]);
       o.guides_set = true;
       o.guides_chain = v == "chain";
+      o.guides_route = v == "route";
     }
     else if (a.rfind("--denoise=", 0) == 0) {
       o.denoise = true;
@@ -292,6 +296,7 @@ int main(int argc, char **argv) {
   std::vector<uint8_t *> d_u8(o.gpus, nullptr);
   uint8_t *d_all = nullptr;
   char *d_guides = nullptr;  // --denoise: hits, position, normal, albedo, then the filter's scratch
+  void *d_route_state = nullptr;  // --denoise-guides=route: rt_route's state
   std::vector<ncclComm_t> comms;
   if (use_rccl) {
     comms.resize(o.gpus);
@@ -321,6 +326,9 @@ int main(int argc, char **argv) {
     const size_t scratch = rt_denoise_scratch_bytes(o.width, o.height);
     if (scratch == 0) die("--denoise: frame size", RT_ERR_INVALID);
     if (hipMalloc(&d_guides, (guide_bytes + 15) / 16 * 16 + scratch) != hipSuccess) die("denoise buffers", RT_ERR_HIP);
+    if (o.guides_route &&
+        hipMalloc(&d_route_state, rt_route_state_bytes(o.width, jobs[0].params.local_rows)) != hipSuccess)
+      die("route state", RT_ERR_HIP);
   }
   // per device: events before the render, after it, after write_color and
   // after the gather, for the per-device lines on stderr
@@ -350,6 +358,13 @@ int main(int argc, char **argv) {
         cb.normal = gb.normal;
         cb.albedo = gb.albedo;
         check(rt_guides_async(ctxs[g], &cam, &jobs[g].params, nullptr, &cb, streams[g]), "rt_guides_async");
+      } else if (o.guides_route) {
+        rt_route_buffers rb{};
+        rb.hits = gb.hits;
+        rb.position = gb.position;
+        rb.normal = gb.normal;
+        rb.albedo = gb.albedo;
+        check(rt_route_async(ctxs[g], &cam, &jobs[g].params, nullptr, &rb, d_route_state, streams[g]), "rt_route_async");
       } else {
         check(rt_aov_async(ctxs[g], &cam, &jobs[g].params, &gb, streams[g]), "rt_aov_async");
       }
@@ -495,6 +510,7 @@ int main(int argc, char **argv) {
     (void)hipFree(d_all);
   }
   (void)hipFree(d_guides);
+  (void)hipFree(d_route_state);
   for (auto *c : ctxs) rt_context_destroy(c);
   if (!o.quiet && !gpu_mode) std::fprintf(stderr, "\nDone.\n");  // main.cc:132
   return 0;

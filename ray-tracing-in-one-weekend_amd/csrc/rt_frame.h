@@ -1,20 +1,21 @@
 // rt_frame.h -- internal: how a pass of a context starts and ends on a stream,
 // and the host helpers its passes share.  A pass over the context's scene (the
 // render in rt_api.cpp, the first-hit feature pass in rt_aov.hip /
-// librtow_aov.so, the chain-following one in rt_guides.hip /
-// librtow_guides.so) begins with rt_internal_frame_begin; an image-space pass
+// librtow_aov.so, the chain-following ones in rt_guides.hip /
+// librtow_guides.so and rt_route.hip / librtow_route.so) begins with
+// rt_internal_frame_begin; an image-space pass
 // that only shares the context's ordering (the denoiser in rt_denoise.hip /
 // librtow_denoise.so, temporal accumulation in rt_temporal.hip /
 // librtow_temporal.so, the resolve in rt_resolve.hip / librtow_resolve.so,
 // upsampling in rt_upscale.hip / librtow_upscale.so) with
 // rt_internal_pass_begin; what those share beyond this header is in rt_post.h
-// and rt_reproject.h, and what the two traced feature passes share (device
-// and host) in rt_trace_pass.h.  The helpers: hip_fail /
+// and rt_reproject.h, and what the traced feature passes share (device
+// and host) in rt_trace_pass.h and rt_chain.h.  The helpers: hip_fail /
 // RT_HIP, the traced passes' cut of a frame's samples into launches
 // (rt_samples_per_launch, rt_sample_ranges: no HIP in them, so that
 // tools/host_sanitize.cpp checks them), rt_pass_scope, rt_device_buf and
 // rt_sync_pass, the one host sequence of the synchronous rt_aov / rt_denoise /
-// rt_temporal / rt_resolve / rt_upscale / rt_guides.  Not
+// rt_temporal / rt_resolve / rt_upscale / rt_guides / rt_route.  Not
 // installed; rt_context stays opaque outside rt_api.cpp, so the other
 // libraries get what they need through rt_frame_setup.
 #ifndef RTOW_RT_FRAME_H

@@ -1,7 +1,7 @@
-// rt_trace_pass.h -- internal: what the two passes that trace the render's rays
+// rt_trace_pass.h -- internal: what the passes that trace the render's rays
 // into feature buffers share (the first-hit pass in rt_aov.hip, the
-// chain-following one in rt_guides.hip; each includes this once, nothing else
-// does).  On the device: the block's LDS copy of the layer grid, the tile ->
+// chain-following ones in rt_guides.hip and rt_route.hip, those two through
+// rt_chain.h as well; each includes this once, nothing else does).  On the device: the block's LDS copy of the layer grid, the tile ->
 // pixel mapping, the run-time choice of closest_hit<>'s fold class, the hit
 // block up to the spurious-root test and from it to the shading normal, and
 // the six sums both passes write.  On the host: the launch table over a
@@ -188,7 +188,7 @@ struct feature_sums {
 
 }  // namespace rtk
 
-// The host half has internal linkage: each of the two libraries keeps its own.
+// The host half has internal linkage: each of the libraries keeps its own.
 namespace {
 
 // A pass's kernel by variant: K<OPEN, BVH, GRID, GP>::kernel is the __global__
@@ -263,6 +263,26 @@ int trace_launches(const rt_frame_setup &fs, const rt_params *prm, std::vector<h
                           });
 }
 
+// The synchronous form of a pass over explicit parts (rt_frame.h's
+// rt_sync_pass): enqueue(fs, prm, dev, events) makes the launches into the
+// parts' device addresses dev[0 .. N), and the pass is waited for launch by
+// launch.
+template <size_t N, class Enqueue>
+int trace_sync(rt_context *c, const rt_camera *cam, const rt_params *prm, const rt_sync_part (&parts)[N],
+               Enqueue enqueue, double *kernel_ms) {
+  std::vector<hipEvent_t> events;
+  const int r = rt_sync_pass(
+      c, cam, prm, parts, kernel_ms,
+      [&](void *const *dev, const rt_frame_setup &fs) { return enqueue(fs, prm, dev, &events); },
+      [&]() -> int {
+        // wait launch by launch: a fault surfaces after the launch it happened in
+        for (hipEvent_t ev : events) RT_HIP(hipEventSynchronize(ev));
+        return RT_OK;
+      });
+  for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+  return r;
+}
+
 // One pass over N buffers (NULL = not wanted; none wanted: nothing to do), of
 // px_bytes[k] bytes per pixel.  enqueue(fs, prm, ptrs, events) makes the launches
 // (trace_launches) into the device pointers ptrs[0 .. N).  host false: the
@@ -283,17 +303,7 @@ int trace_pass(rt_context *c, const rt_camera *cam, const rt_params *prm, void *
   }
   rt_sync_part parts[N];
   for (size_t k = 0; k < N; ++k) parts[k] = {bufs[k] ? px_bytes[k] * npx : 0, nullptr, bufs[k]};
-  std::vector<hipEvent_t> events;
-  const int r = rt_sync_pass(
-      c, cam, prm, parts, kernel_ms,
-      [&](void *const *dev, const rt_frame_setup &fs) { return enqueue(fs, prm, dev, &events); },
-      [&]() -> int {
-        // wait launch by launch: a fault surfaces after the launch it happened in
-        for (hipEvent_t ev : events) RT_HIP(hipEventSynchronize(ev));
-        return RT_OK;
-      });
-  for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-  return r;
+  return trace_sync(c, cam, prm, parts, enqueue, kernel_ms);
 }
 
 }  // namespace

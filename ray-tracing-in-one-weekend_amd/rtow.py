@@ -35,6 +35,8 @@ RESOLVE_LIB_PATH = os.path.join(HERE, "librtow_resolve.so")
 UPSCALE_LIB_PATH = os.path.join(HERE, "librtow_upscale.so")
 # feature buffers that follow mirror and glass paths (include/rt_guides.h): a seventh
 GUIDES_LIB_PATH = os.path.join(HERE, "librtow_guides.so")
+# guide buffers of each pixel's dominant specular route (include/rt_route.h): an eighth
+ROUTE_LIB_PATH = os.path.join(HERE, "librtow_route.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
@@ -81,6 +83,12 @@ GUIDES_VERSION = 1  # include/rt_guides.h RT_GUIDES_VERSION
 GUIDES_FIELDS = AOV_FIELDS + (("bounces", np.uint32, 1), ("escaped", np.uint32, 1))
 GUIDES_DEFAULTS = {"max_bounces": 8, "max_fuzz": 0.0}
 GUIDES_MAX_BOUNCES = 64
+ROUTE_VERSION = 1  # include/rt_route.h RT_ROUTE_VERSION
+# rt_route_buffers' output fields in order: rt_aov_buffers', then the dominant route and its sample count (a
+# ninth pointer, "state", takes rt_route's final state); the options and their rules are rt_guides'
+ROUTE_FIELDS = AOV_FIELDS + (("route", np.uint32, 1), ("matched", np.uint32, 1))
+ROUTE_STATE_BYTES_PER_PIXEL = 64  # RT_ROUTE_STATE_BYTES_PER_PIXEL: four planes of 16-byte entries
+ROUTE_NO_HIT = 0xFFFFFFFF  # "route" of a pixel without a hit sample
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
 RT_OPT_BVH_COLLAPSE, RT_OPT_BVH_SIDE, RT_OPT_LAUNCH_SAMPLES, RT_OPT_GRID_FIT = 4, 5, 6, 7
@@ -146,6 +154,16 @@ class GuidesOptions(ctypes.Structure):
     _fields_ = [("max_bounces", ctypes.c_int32), ("max_fuzz", ctypes.c_float), ("reserved", ctypes.c_uint32)]
 
 
+class RouteBuffers(ctypes.Structure):
+    """rt_route_buffers: device (rt_route_async) or host (rt_route) pointers, NULL = not wanted; state: rt_route only."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in ROUTE_FIELDS] + [("state", ctypes.c_void_p)]
+
+
+class RouteOptions(ctypes.Structure):
+    """rt_route_options: max_bounces (0 = default, -1 = none), max_fuzz, reserved."""
+    _fields_ = [("max_bounces", ctypes.c_int32), ("max_fuzz", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+
 class DenoiseDesc(ctypes.Structure):
     """rt_denoise_desc: the frame, the options (0 = default) and device
     (rt_denoise_async) or host (rt_denoise) pointers."""
@@ -203,6 +221,7 @@ _temporal_lib = None
 _resolve_lib = None
 _upscale_lib = None
 _guides_lib = None
+_route_lib = None
 
 
 def _missing(path):
@@ -435,6 +454,27 @@ def guides_options(max_bounces=None, max_fuzz=None):
             raise ValueError("max_fuzz must be >= 0")
         o.max_fuzz = float(max_fuzz)
     return o
+
+
+def route_lib():
+    """Load librtow_route.so, the feature pass of each pixel's dominant
+    specular route (raises if it has not been built)."""
+    global _route_lib
+    if _route_lib is None:
+        head = [ctypes.c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Params), ctypes.POINTER(RouteOptions),
+                ctypes.POINTER(RouteBuffers)]
+        _route_lib = _load_pass(ROUTE_LIB_PATH, "rt_route_version", ROUTE_VERSION, {
+            "rt_route_state_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+            "rt_route_async": (None, head + [ctypes.c_void_p, ctypes.c_void_p]),
+            "rt_route": (None, head + [ctypes.POINTER(ctypes.c_double)])})
+    return _route_lib
+
+
+def route_options(max_bounces=None, max_fuzz=None):
+    """A RouteOptions, under guides_options' rules: None takes the default
+    (GUIDES_DEFAULTS), a value means itself, max_bounces=0 follows nothing."""
+    g = guides_options(max_bounces, max_fuzz)
+    return RouteOptions(max_bounces=g.max_bounces, max_fuzz=g.max_fuzz, reserved=0)
 
 
 def aov_lib():
@@ -737,10 +777,14 @@ class Context:
                                     ctypes.c_void_p(dev_ptr), ctypes.c_void_p(stream)),
               "rt_render_async")
 
-    def _feature_pass(self, fields, buffers_type, call, name, cam, params, which, opts=()):
-        """Context.aov / Context.guides: the wanted host arrays, the call, the dict."""
+    def _feature_pass(self, fields, buffers_type, call, name, cam, params, which, opts=(), extra=None):
+        """Context.aov / Context.guides / Context.route: the wanted host arrays
+        (extra: further ones of the caller's own shape, by field name), the
+        call, the dict."""
         _reject_unknown(which, [f[0] for f in fields], "feature buffers")
-        out, bufs = {}, buffers_type()
+        out, bufs = dict(extra or {}), buffers_type()
+        for field, a in out.items():
+            setattr(bufs, field, a.ctypes.data)
         for field, dt, ch in fields:
             if field in which:
                 shape = (params.local_rows, params.width) + ((3,) if ch == 3 else ())
@@ -794,6 +838,36 @@ class Context:
         opts = guides_options(max_bounces, max_fuzz)
         self._feature_pass_async(GUIDES_FIELDS, GuidesBuffers, guides_lib().rt_guides_async, "rt_guides_async", cam,
                                  params, dev_ptrs, stream, (ctypes.byref(opts),))
+
+    def route(self, cam, params, which=tuple(f[0] for f in ROUTE_FIELDS), max_bounces=None, max_fuzz=None):
+        """Guide buffers of each pixel's dominant specular route (rt_route,
+        include/rt_route.h), synchronously: Context.aov's dict (the same keys,
+        layout and sum contract: the dominant route's mean features times
+        "hits") plus "route" ((bounces << 1) | escaped of that route,
+        ROUTE_NO_HIT without a hit) and "matched" (the samples the mean is
+        over).  "state" in `which` adds the pass's final per-pixel state, uint32
+        (4, local_rows, W, 4): the four planes of 16-byte entries the header
+        documents.  Options: see route_options."""
+        names = [f[0] for f in ROUTE_FIELDS]
+        _reject_unknown(which, names + ["state"], "feature buffers")
+        opts = route_options(max_bounces, max_fuzz)
+        extra = {"state": np.zeros((4, params.local_rows, params.width, 4), np.uint32)} if "state" in which else None
+        return self._feature_pass(ROUTE_FIELDS, RouteBuffers, route_lib().rt_route, "rt_route", cam, params,
+                                  [n for n in which if n != "state"], (ctypes.byref(opts),), extra)
+
+    def route_async(self, cam, params, dev_ptrs, state, stream=0, max_bounces=None, max_fuzz=None):
+        """Enqueue the pass (rt_route_async) into raw device pointers (e.g.
+        torch tensor.data_ptr()): dev_ptrs maps names of ROUTE_FIELDS to device
+        pointers, names left out are not computed; state is device memory of
+        route_lib().rt_route_state_bytes(W, local_rows) bytes, 16-byte aligned,
+        that the pass works in and leaves its final state in."""
+        _reject_unknown(dev_ptrs, [f[0] for f in ROUTE_FIELDS], "feature buffers")
+        opts = route_options(max_bounces, max_fuzz)
+
+        def call(h, c, p, o, b, s):
+            return route_lib().rt_route_async(h, c, p, o, b, ctypes.c_void_p(state), s)
+        self._feature_pass_async(ROUTE_FIELDS, RouteBuffers, call, "rt_route_async", cam, params, dev_ptrs, stream,
+                                 (ctypes.byref(opts),))
 
     def denoise(self, beauty, aov, spp, **options):
         """The guided a-trous filter (rt_denoise, include/rt_denoise.h),
