@@ -16,7 +16,14 @@
  *    candidate rule and RT_FLAG_OPEN_INTERVAL choice, the same refined root,
  *    and the render's rule for a spurious root (a refined root before t_min
  *    on a sphere the ray moves away from: the ray walks again from the scan's
- *    root point, and that walk is not a segment).
+ *    root point, and that walk is not a segment).  Such a skipped primary ray
+ *    keeps its direction's bits here, where the passes that follow the chain
+ *    beyond the first hit normalise it again, their one exception in
+ *    principle to equality with this pass.  tests/test_features_oracle_gpu.py
+ *    compares this pass with the oracle's form of the same name
+ *    (test_aov_is_the_oracles, RTO_TERM_KEEP_DIR) and the chain passes with
+ *    the other; no primary ray of its cases takes such a skip, so neither
+ *    form is pinned yet.
  *  - rt_params.max_depth and RT_FLAG_METAL_UNIT_VECTOR are ignored.  The
  *    acceleration flags select the walk exactly as in a render
  *    (RT_FLAG_ACCEL_BVH, RT_FLAG_LAYER_BVH, the context's grid placement);

@@ -56,6 +56,11 @@
  *    it leaves is skipped as the render skips it, with the direction
  *    normalised again, where rt_aov keeps the direction's bits; the walk that
  *    follows may then differ in the last bit and, at a limb, in what it hits.
+ *    The CPU oracle models both forms (oracle/rt_oracle.h, RTO_TERM_KEEP_DIR),
+ *    and tests/test_features_oracle_gpu.py compares this pass with the
+ *    renormalising one (test_guides_are_the_oracles) and rt_aov with the other
+ *    (test_aov_is_the_oracles); no primary ray of its cases takes such a skip,
+ *    so neither form is pinned yet and the exception stays one in principle.
  *  - rt_params.max_depth is ignored (max_bounces bounds the chain); the
  *    acceleration flags select the walk exactly as in a render; the other
  *    bookkeeping and scheduling flags and rt_params.units are ignored, and the

@@ -60,7 +60,11 @@
  *    0xFFFFFFFF.  Padding rows (the frame contract of rt.h) get the same.
  *  - Consequences.  With max_bounces = -1 every key is 1, so the six shared
  *    buffers are rt_aov's bytes (but for rt_aov's one exception in principle,
- *    a primary ray starting within t_min of a sphere it leaves).  Wherever
+ *    a primary ray starting within t_min of a sphere it leaves: this pass
+ *    normalises the skipped direction again, rt_aov keeps its bits;
+ *    tests/test_features_oracle_gpu.py compares each pass with the oracle's
+ *    form of it, but no primary ray of its cases takes such a skip, so
+ *    neither form is pinned yet).  Wherever
  *    matched == hits and the candidate never changed, the six are the
  *    chain-following pass's bytes.  hits is rt_aov's at every setting.
  *  - rt_params.max_depth, units and the bookkeeping and scheduling flags are

@@ -18,7 +18,10 @@
 //    expanded quadratic, pcg4d counter RNG, closed-form sampling.  Written
 //    independently of ray-tracing-in-one-weekend_amd/csrc/rt_render.hip from
 //    the same specification; with -ffp-contract=off and explicit fmaf it is
-//    the bit-exact per-pixel parity partner of the GPU kernel.
+//    the bit-exact per-pixel parity partner of the GPU kernel.  One step of
+//    its segment loop is kernel_step; kernel_pixel (the render) and
+//    chain_sample (rto_kernel_terminals: the per-sample terminals rt_aov,
+//    rt_guides and rt_route are checked against) both run on it.
 //
 // Reference anchors are cited per function (paths under /root/reference).
 #include "rt_oracle.h"
@@ -445,11 +448,249 @@ float camera_ray(const kctx &k, uint32_t pix, int col, int grow, uint32_t sample
   return tmin_of(k.tmin_world, normalize3(d[0], d[1], d[2]));
 }
 
+// ---------------------------------------------------------------------
+// One step of the kernel algorithm's segment loop, shared by the render
+// restatement (kernel_pixel) and the chain restatement (chain_sample): the
+// closest hit, the refined root, the spurious-root test with both arms, the
+// hit point, the face rule and the shading normal, and the three materials'
+// scatter directions with the metal's absorption test.  What a caller does
+// with a step -- the throughput, the depth count, the sky, whether the path
+// goes on -- is the caller's.
+struct kray {
+  float o[3], d[3];
+  float tmin;
+  long origin_sphere;  // the sphere the ray starts on (-1: a camera ray)
+};
+enum { KSTEP_MISS = 0, KSTEP_SKIP = 1, KSTEP_HIT = 2 };
+enum { KDIEL_REFRACT = 1, KDIEL_SCHLICK = 2, KDIEL_TIR = 3 };
+struct kstep {
+  long best;     // the winner (-1: none)
+  bool near;     // which root the winner was taken at
+  float tmax;    // the scan's root
+  float t;       // the refined root
+  int arm;       // KSTEP_SKIP: 1 = refined root before t_min, 2 = the same sphere's exiting root
+  bool front;    // KSTEP_HIT from here on
+  float p[3], nn[3];
+  float sd[3];   // the scatter direction, not normalised
+  bool scattered;
+  int diel;      // a dielectric's choice (KDIEL_*), 0 otherwise
+};
+
+// depth: counted hits before this one (the hit draws pcg4d(pix, sample, depth + 1)).
+// KSTEP_SKIP: the ray has been moved on (arm 1: its origin to the scan's root
+// point; arm 2: its t_min just past the scan's root); the caller normalises the
+// direction again, or keeps its bits.  tr: print the step (rto_trace).
+int kernel_step(const kctx &k, kray &ray, uint32_t pix, uint32_t sample, int depth, bool tr, kstep &st) {
+  const kscene &sc = *k.sc;
+  const size_t n = sc.cx.size();
+  float *const o = ray.o, *const d = ray.d;
+  const float tmin = ray.tmin;
+  // closest hit: expanded quadratic with |d| = 1
+  const float nk1 = -dot3(o[0], o[1], o[2], d[0], d[1], d[2]);
+  const float o2 = dot3(o[0], o[1], o[2], o[0], o[1], o[2]);
+  const float ox2 = -2.0f * o[0], oy2 = -2.0f * o[1], oz2 = -2.0f * o[2];
+  float tmax = INFINITY;
+  long best = -1;
+  bool near = true;  // which root the winner was taken at
+  if (tr)
+    std::fprintf(g_trace, "seg %d O=(%.9g %.9g %.9g) D=(%.9g %.9g %.9g) |O|^2=%.9g\n", depth, o[0], o[1], o[2],
+                 d[0], d[1], d[2], o2);
+  {
+    // the per-sphere test in blocks of 64: a branch-free pass the compiler
+    // vectorises (h and the discriminant's excess for every sphere), then
+    // the candidates in index order -- the same arithmetic per sphere
+    constexpr size_t kB = 64;
+    float hb[kB], eb[kB];
+    for (size_t i0 = 0; i0 < n; i0 += kB) {
+      const size_t m = std::min(kB, n - i0);
+      const float *cx = &sc.cx[i0], *cy = &sc.cy[i0], *cz = &sc.cz[i0], *ks = &sc.ks[i0];
+      for (size_t j = 0; j < m; ++j) {
+        const float h = fmaf_(cz[j], d[2], fmaf_(cx[j], d[0], fmaf_(cy[j], d[1], nk1)));
+        const float g = fmaf_(cz[j], oz2, fmaf_(cx[j], ox2, fmaf_(cy[j], oy2, o2)));
+        hb[j] = h;
+        eb[j] = fmaf_(h, h, -g) - ks[j];  // >= 0 <=> e >= ks (exact for finite floats)
+      }
+      for (size_t j = 0; j < m; ++j) {
+        if (!(eb[j] >= 0.0f)) continue;
+        const size_t i = i0 + j;
+        const float h = hb[j];
+        // sphere.h:34-44: the root offered is t0 if past t_min, else t1; it
+        // wins if closer than tmax (ties: last index for the closed src/cpu
+        // interval, first for the open src/gpu one -- what a sequential scan
+        // does, stated so that any visiting order gives the same winner)
+        const float sq = sqrt_k(eb[j]);
+        float t0 = h - sq, t1 = h + sq;
+        if (k.fp64_roots) {  // the same ray and sphere, roots in fp64
+          const double ocx = (double)o[0] - sc.cx[i], ocy = (double)o[1] - sc.cy[i], ocz = (double)o[2] - sc.cz[i];
+          const double b = ocx * d[0] + ocy * d[1] + ocz * d[2];
+          const double r = sc.radius[i];
+          const double c = ocx * ocx + ocy * ocy + ocz * ocz - r * r;
+          const double dd = b * b - c;
+          if (!(dd >= 0.0)) continue;
+          const double s = std::sqrt(dd);
+          t0 = (float)(-b - s);
+          t1 = (float)(-b + s);
+        }
+        const bool use0 = k.open ? t0 > tmin : t0 >= tmin;
+        const float root = use0 ? t0 : t1;
+        const bool above = k.open ? root > tmin : root >= tmin;
+        const bool closer = root < tmax || (root == tmax && (k.open ? (long)i < best : (long)i > best));
+        if (tr)
+          std::fprintf(g_trace, "   cand %zu disc=%.9g t0=%.9g t1=%.9g root=%.9g above=%d closer=%d\n", i, eb[j], t0,
+                       t1, root, (int)above, (int)closer);
+        if (above && closer) {
+          tmax = root;
+          near = use0;
+          best = (long)i;
+        }
+      }
+    }
+  }
+  st.best = best;
+  st.near = near;
+  st.tmax = tmax;
+  st.t = 0.0f;
+  st.arm = 0;
+  st.diel = 0;
+  if (best < 0) {
+    if (tr) std::fprintf(g_trace, "  -> best %ld t %.9g near %d\n", best, tmax, (int)near);
+    return KSTEP_MISS;
+  }
+  const size_t b = (size_t)best;
+  float t = tmax, bb;
+  {
+    // refine the winner's chosen root with the better-conditioned forms
+    // (DESIGN.md "Kernel algorithm", step 3); bb = (O - C).D
+    const float r2 = sc.radius[b] * sc.radius[b];
+    const float ocx = o[0] - sc.cx[b], ocy = o[1] - sc.cy[b], ocz = o[2] - sc.cz[b];
+    bb = dot3(ocx, ocy, ocz, d[0], d[1], d[2]);
+    float cc;
+    if (r2 < o2 + std::fabs(sc.ks[b])) {
+      cc = fmaf_(ocz, ocz, fmaf_(ocy, ocy, fmaf_(ocx, ocx, -r2)));
+    } else {
+      const float g = fmaf_(sc.cz[b], oz2, fmaf_(sc.cy[b], oy2, fmaf_(sc.cx[b], ox2, o2)));
+      cc = g + sc.ks[b];
+    }
+    float disc;
+    if (r2 < bb * bb) {
+      const float fx = fmaf_(-bb, d[0], ocx), fy = fmaf_(-bb, d[1], ocy), fz = fmaf_(-bb, d[2], ocz);
+      disc = fmaf_(-fz, fz, fmaf_(-fy, fy, fmaf_(-fx, fx, r2)));
+    } else {
+      disc = fmaf_(bb, bb, -cc);
+    }
+    const float sq = sqrt_k(disc);
+    const float q = -(bb + (bb < 0.0f ? -sq : sq));
+    if (q != 0.0f) {
+      const float ta = q, tb = cc * (1.0f / q);  // c RN(1/q), the kernel's rcp_k
+      const float tref = near ? std::fmin(ta, tb) : std::fmax(ta, tb);
+      if (std::isfinite(tref)) t = tref;
+    }
+  }
+  st.t = t;
+  // A refined root before t_min on a sphere the ray moves away from: the
+  // ray starts on that sphere and leaves its ball, which in exact
+  // arithmetic it cannot meet again (src/cpu, fp64, never does at
+  // t >= 0.001); the expanded quadratic's root was an fp32 artefact (for
+  // spheres far from the origin it can trap the path inside the
+  // sphere).  So is (round 5) the exiting root of the sphere the ray
+  // starts on when it moves away from that sphere's centre: t = 0 in
+  // exact arithmetic, an fp32 hit point an ulp inside the ball with a
+  // tiny t_min (lambertian n + u, u ~ -n) otherwise.  Not a segment: the
+  // ray moves on to the scan's root point and walks again, same
+  // direction.  (the ray keeps its t_min: same direction, same unit)
+  if (bb > 0.0f && (t < tmin || (k.same_exit && best == ray.origin_sphere && !near))) {
+    if (tr) std::fprintf(g_trace, "  spurious best %ld t %.9g: skipped\n", best, tmax);
+    if (t < tmin) {
+      st.arm = 1;
+      for (int a = 0; a < 3; ++a) o[a] = fmaf_(tmax, d[a], o[a]);
+    } else {  // the same origin, t_min just past the scan's root (the kernel's bit step)
+      st.arm = 2;
+      ray.tmin = std::nextafter(tmax, INFINITY);
+    }
+    return KSTEP_SKIP;
+  }
+  if (tr) std::fprintf(g_trace, "  -> best %ld t %.9g near %d\n", best, tmax, (int)near);
+  float *const p = st.p, *const nn = st.nn, *const sd = st.sd;
+  for (int a = 0; a < 3; ++a) p[a] = fmaf_(t, d[a], o[a]);
+  nn[0] = (p[0] - sc.cx[b]) * sc.inv_r[b];
+  nn[1] = (p[1] - sc.cy[b]) * sc.inv_r[b];
+  nn[2] = (p[2] - sc.cz[b]) * sc.inv_r[b];
+  if (k.fp64_hit) {
+    // attribution only (RTO_OPT_FP64_HIT): the winner's root from the
+    // fp64 quadratic on the fp32 ray and sphere (the reference's
+    // sphere::hit arithmetic, sphere.h:24-51, |d| = 1 here), and the hit
+    // point and normal from it in fp64, rounded once to fp32
+    const double c3[3] = {sc.cx[b], sc.cy[b], sc.cz[b]}, rr = sc.radius[b];
+    double oc[3], hb = 0.0, cq = -rr * rr, dd = 0.0;
+    for (int a = 0; a < 3; ++a) {
+      oc[a] = (double)o[a] - c3[a];
+      hb += oc[a] * (double)d[a];
+      cq += oc[a] * oc[a];
+      dd += (double)d[a] * (double)d[a];
+    }
+    const double disc = hb * hb - dd * cq;
+    if (disc >= 0.0) {
+      const double sq = std::sqrt(disc);
+      const double td = (near ? (-hb - sq) : (-hb + sq)) / dd;
+      for (int a = 0; a < 3; ++a) {
+        const double pd = (double)o[a] + td * (double)d[a];
+        p[a] = (float)pd;
+        nn[a] = (float)((pd - c3[a]) / rr);
+      }
+    }
+  }
+  // front face from the root taken (exact-arithmetic equivalent of
+  // dot(d, outward) < 0, hittable.h:16-19; outward flips for r < 0)
+  const bool front = near != (sc.inv_r[b] < 0.0f);
+  st.front = front;
+  if (!front)
+    for (int a = 0; a < 3; ++a) nn[a] = -nn[a];
+  const u4 r = pcg4d(pix, sample, (uint32_t)(depth + 1), k.seed32);
+  st.scattered = true;
+  if (sc.kind[b] == RT_LAMBERTIAN) {
+    float u[3];
+    unit_vec(unif(r.x), unif(r.y), u[0], u[1], u[2]);
+    for (int a = 0; a < 3; ++a) sd[a] = nn[a] + u[a];
+    const float eps = 1e-8f;
+    if (std::fabs(sd[0]) < eps && std::fabs(sd[1]) < eps && std::fabs(sd[2]) < eps)
+      for (int a = 0; a < 3; ++a) sd[a] = nn[a];
+  } else if (sc.kind[b] == RT_METAL) {
+    const float kk = -2.0f * dot3(d[0], d[1], d[2], nn[0], nn[1], nn[2]);
+    float rf[3], u[3];
+    for (int a = 0; a < 3; ++a) rf[a] = fmaf_(kk, nn[a], d[a]);
+    unit_vec(unif(r.x), unif(r.y), u[0], u[1], u[2]);
+    float fz = sc.param[b];
+    if (!k.metal_unit) fz *= ball_radius(r);
+    for (int a = 0; a < 3; ++a) sd[a] = fmaf_(fz, u[a], rf[a]);
+    st.scattered = dot3(sd[0], sd[1], sd[2], nn[0], nn[1], nn[2]) > 0.0f;
+  } else {
+    const float ratio = front ? sc.inv_param[b] : sc.param[b];
+    const float cos_t = std::fmin(-dot3(d[0], d[1], d[2], nn[0], nn[1], nn[2]), 1.0f);
+    // ratio sin > 1 (material.h:64), squared (the kernel's form)
+    const bool cannot = (ratio * ratio) * fmaf_(-cos_t, cos_t, 1.0f) > 1.0f;
+    const float r0 = sc.r0[b];  // ((1-ior)/(1+ior))^2, same for ior and 1/ior
+    const float x = 1.0f - cos_t;
+    const float x2 = x * x;
+    const float refl = fmaf_(1.0f - r0, x2 * x2 * x, r0);
+    if (cannot || refl > unif(r.x)) {
+      st.diel = cannot ? KDIEL_TIR : KDIEL_SCHLICK;
+      const float kk = -2.0f * dot3(d[0], d[1], d[2], nn[0], nn[1], nn[2]);
+      for (int a = 0; a < 3; ++a) sd[a] = fmaf_(kk, nn[a], d[a]);
+    } else {
+      st.diel = KDIEL_REFRACT;
+      float q[3];
+      for (int a = 0; a < 3; ++a) q[a] = ratio * fmaf_(cos_t, nn[a], d[a]);
+      const float m = -sqrt_k(std::fabs(1.0f - dot3(q[0], q[1], q[2], q[0], q[1], q[2])));
+      for (int a = 0; a < 3; ++a) sd[a] = fmaf_(m, nn[a], q[a]);
+    }
+  }
+  return KSTEP_HIT;
+}
+
 // one pixel, all samples; returns number of closest-hit queries
 unsigned long long kernel_pixel(const kctx &k, int col, int grow, float acc[3]) {
   const kscene &sc = *k.sc;
   const uint32_t pix = (uint32_t)grow * (uint32_t)k.p->width + (uint32_t)col;
-  const size_t n = sc.cx.size();
   unsigned long long segs = 0;
   // fixed-point pixel sum (the kernel's spec): a sample's
   // radiance v (at most 1) adds q(v 2^F) to a uint32 sum, F = 31 -
@@ -480,145 +721,26 @@ unsigned long long kernel_pixel(const kctx &k, int col, int grow, float acc[3]) 
   const bool dither = f < 20 && !k.no_dither;
   uint64_t q[3] = {0u, 0u, 0u};
   for (uint32_t sample = 0; sample < (uint32_t)k.p->spp; ++sample) {
-    float o[3], d[3];
-    float tmin = camera_ray(k, pix, col, grow, sample, o, d);
+    kray ray;
+    ray.tmin = camera_ray(k, pix, col, grow, sample, ray.o, ray.d);
+    ray.origin_sphere = -1;
     float th[3] = {1.0f, 1.0f, 1.0f};
     bool after_skip = false, inner_seen = false;  // rto_kernel_attrib
     long prev_best = -2;
-    long origin_sphere = -1;  // the sphere the ray starts on (-1: a camera ray)
+    const bool tr = g_trace && (long)sample == g_trace_sample;
     for (int depth = 0;;) {
       ++segs;
-      // closest hit: expanded quadratic with |d| = 1
-      const float nk1 = -dot3(o[0], o[1], o[2], d[0], d[1], d[2]);
-      const float o2 = dot3(o[0], o[1], o[2], o[0], o[1], o[2]);
-      const float ox2 = -2.0f * o[0], oy2 = -2.0f * o[1], oz2 = -2.0f * o[2];
-      float tmax = INFINITY;
-      long best = -1;
-      bool near = true;  // which root the winner was taken at
-      const bool tr = g_trace && (long)sample == g_trace_sample;
-      if (tr)
-        std::fprintf(g_trace, "seg %d O=(%.9g %.9g %.9g) D=(%.9g %.9g %.9g) |O|^2=%.9g\n", depth, o[0],
-                     o[1], o[2], d[0], d[1], d[2], o2);
-      auto closest = [&]() {
-        tmax = INFINITY;
-        best = -1;
-        near = true;
-        // the per-sphere test in blocks of 64: a branch-free pass the compiler
-        // vectorises (h and the discriminant's excess for every sphere), then
-        // the candidates in index order -- the same arithmetic per sphere
-        constexpr size_t kB = 64;
-        float hb[kB], eb[kB];
-        for (size_t i0 = 0; i0 < n; i0 += kB) {
-          const size_t m = std::min(kB, n - i0);
-          const float *cx = &sc.cx[i0], *cy = &sc.cy[i0], *cz = &sc.cz[i0], *ks = &sc.ks[i0];
-          for (size_t j = 0; j < m; ++j) {
-            const float h = fmaf_(cz[j], d[2], fmaf_(cx[j], d[0], fmaf_(cy[j], d[1], nk1)));
-            const float g = fmaf_(cz[j], oz2, fmaf_(cx[j], ox2, fmaf_(cy[j], oy2, o2)));
-            hb[j] = h;
-            eb[j] = fmaf_(h, h, -g) - ks[j];  // >= 0 <=> e >= ks (exact for finite floats)
-          }
-          for (size_t j = 0; j < m; ++j) {
-          if (!(eb[j] >= 0.0f)) continue;
-          const size_t i = i0 + j;
-          const float h = hb[j];
-          {
-            // sphere.h:34-44: the root offered is t0 if past t_min, else t1; it
-            // wins if closer than tmax (ties: last index for the closed src/cpu
-            // interval, first for the open src/gpu one -- what a sequential scan
-            // does, stated so that any visiting order gives the same winner)
-            const float sq = sqrt_k(eb[j]);
-            float t0 = h - sq, t1 = h + sq;
-            if (k.fp64_roots) {  // the same ray and sphere, roots in fp64
-              const double ocx = (double)o[0] - sc.cx[i], ocy = (double)o[1] - sc.cy[i], ocz = (double)o[2] - sc.cz[i];
-              const double b = ocx * d[0] + ocy * d[1] + ocz * d[2];
-              const double r = sc.radius[i];
-              const double c = ocx * ocx + ocy * ocy + ocz * ocz - r * r;
-              const double dd = b * b - c;
-              if (!(dd >= 0.0)) continue;
-              const double s = std::sqrt(dd);
-              t0 = (float)(-b - s);
-              t1 = (float)(-b + s);
-            }
-            const bool use0 = k.open ? t0 > tmin : t0 >= tmin;
-            const float root = use0 ? t0 : t1;
-            const bool above = k.open ? root > tmin : root >= tmin;
-            const bool closer = root < tmax || (root == tmax && (k.open ? (long)i < best : (long)i > best));
-            if (tr)
-              std::fprintf(g_trace, "   cand %zu disc=%.9g t0=%.9g t1=%.9g root=%.9g above=%d closer=%d\n", i,
-                           eb[j], t0, t1, root, (int)above, (int)closer);
-            if (above && closer) {
-              tmax = root;
-              near = use0;
-              best = (long)i;
-            }
-          }
-          }
-        }
-      };
-      // refine the winner's chosen root with the better-conditioned forms
-      // (DESIGN.md "Kernel algorithm", step 3); bb = (O - C).D
-      auto refine = [&](size_t b, float &bb) {
-        float t = tmax;
-        const float r2 = sc.radius[b] * sc.radius[b];
-        const float ocx = o[0] - sc.cx[b], ocy = o[1] - sc.cy[b], ocz = o[2] - sc.cz[b];
-        bb = dot3(ocx, ocy, ocz, d[0], d[1], d[2]);
-        float cc;
-        if (r2 < o2 + std::fabs(sc.ks[b])) {
-          cc = fmaf_(ocz, ocz, fmaf_(ocy, ocy, fmaf_(ocx, ocx, -r2)));
-        } else {
-          const float g = fmaf_(sc.cz[b], oz2, fmaf_(sc.cy[b], oy2, fmaf_(sc.cx[b], ox2, o2)));
-          cc = g + sc.ks[b];
-        }
-        float disc;
-        if (r2 < bb * bb) {
-          const float fx = fmaf_(-bb, d[0], ocx), fy = fmaf_(-bb, d[1], ocy),
-                      fz = fmaf_(-bb, d[2], ocz);
-          disc = fmaf_(-fz, fz, fmaf_(-fy, fy, fmaf_(-fx, fx, r2)));
-        } else {
-          disc = fmaf_(bb, bb, -cc);
-        }
-        const float sq = sqrt_k(disc);
-        const float q = -(bb + (bb < 0.0f ? -sq : sq));
-        if (q != 0.0f) {
-          const float ta = q, tb = cc * (1.0f / q);  // c RN(1/q), the kernel's rcp_k
-          const float tr = near ? std::fmin(ta, tb) : std::fmax(ta, tb);
-          if (std::isfinite(tr)) t = tr;
-        }
-        return t;
-      };
-      closest();
-      float t = 0.0f;
-      if (best >= 0) {
-        float bb;
-        t = refine((size_t)best, bb);
-        // A refined root before t_min on a sphere the ray moves away from: the
-        // ray starts on that sphere and leaves its ball, which in exact
-        // arithmetic it cannot meet again (src/cpu, fp64, never does at
-        // t >= 0.001); the expanded quadratic's root was an fp32 artefact (for
-        // spheres far from the origin it can trap the path inside the
-        // sphere).  So is (round 5) the exiting root of the sphere the ray
-        // starts on when it moves away from that sphere's centre: t = 0 in
-        // exact arithmetic, an fp32 hit point an ulp inside the ball with a
-        // tiny t_min (lambertian n + u, u ~ -n) otherwise.  Not a segment: the
-        // ray moves on to the scan's root point and walks again, same
-        // direction.  (the ray keeps its t_min: same direction, same unit)
-        if (bb > 0.0f && (t < tmin || (k.same_exit && best == origin_sphere && !near))) {
-          if (tr) std::fprintf(g_trace, "  spurious best %ld t %.9g: skipped\n", best, tmax);
-          g_skips.fetch_add(1, std::memory_order_relaxed);
-          after_skip = true;
-          if (t < tmin) {
-            for (int a = 0; a < 3; ++a) o[a] = fmaf_(tmax, d[a], o[a]);
-          } else {  // the same origin, t_min just past the scan's root (the kernel's bit step)
-            tmin = std::nextafter(tmax, INFINITY);
-          }
-          normalize3(d[0], d[1], d[2]);
-          --segs;
-          continue;
-        }
+      kstep st;
+      const int what = kernel_step(k, ray, pix, sample, depth, tr, st);
+      if (what == KSTEP_SKIP) {  // not a segment: the ray walks again, its direction normalised again
+        g_skips.fetch_add(1, std::memory_order_relaxed);
+        after_skip = true;
+        normalize3(ray.d[0], ray.d[1], ray.d[2]);
+        --segs;
+        continue;
       }
-      if (tr) std::fprintf(g_trace, "  -> best %ld t %.9g near %d\n", best, tmax, (int)near);
-      if (best < 0) {  // sky, main.cc:27-29
-        const float a = 0.5f * (d[1] + 1.0f);
+      if (what == KSTEP_MISS) {  // sky, main.cc:27-29
+        const float a = 0.5f * (ray.d[1] + 1.0f);
         const float s0 = 1.0f - a;
         const float v[3] = {th[0] * fmaf_(a, 0.5f, s0), th[1] * fmaf_(a, 0.7f, s0), th[2] * (s0 + a)};
         const float u = dither ? dither_u(pix, sample, k.seed32) : 0.0f;
@@ -630,84 +752,13 @@ unsigned long long kernel_pixel(const kctx &k, int col, int grow, float acc[3]) 
         }
         break;
       }
-      const size_t b = (size_t)best;
-      float p[3], nn[3];
-      for (int a = 0; a < 3; ++a) p[a] = fmaf_(t, d[a], o[a]);
-      nn[0] = (p[0] - sc.cx[b]) * sc.inv_r[b];
-      nn[1] = (p[1] - sc.cy[b]) * sc.inv_r[b];
-      nn[2] = (p[2] - sc.cz[b]) * sc.inv_r[b];
-      // front face from the root taken (exact-arithmetic equivalent of
-      // dot(d, outward) < 0, hittable.h:16-19; outward flips for r < 0)
-      if (k.fp64_hit) {
-        // attribution only (RTO_OPT_FP64_HIT): the winner's root from the
-        // fp64 quadratic on the fp32 ray and sphere (the reference's
-        // sphere::hit arithmetic, sphere.h:24-51, |d| = 1 here), and the hit
-        // point and normal from it in fp64, rounded once to fp32
-        const double c3[3] = {sc.cx[b], sc.cy[b], sc.cz[b]}, rr = sc.radius[b];
-        double oc[3], hb = 0.0, cq = -rr * rr, dd = 0.0;
-        for (int a = 0; a < 3; ++a) {
-          oc[a] = (double)o[a] - c3[a];
-          hb += oc[a] * (double)d[a];
-          cq += oc[a] * oc[a];
-          dd += (double)d[a] * (double)d[a];
-        }
-        const double disc = hb * hb - dd * cq;
-        if (disc >= 0.0) {
-          const double sq = std::sqrt(disc);
-          const double td = (near ? (-hb - sq) : (-hb + sq)) / dd;
-          for (int a = 0; a < 3; ++a) {
-            const double pd = (double)o[a] + td * (double)d[a];
-            p[a] = (float)pd;
-            nn[a] = (float)((pd - c3[a]) / rr);
-          }
-        }
-      }
-      const bool front = near != (sc.inv_r[b] < 0.0f);
-      if (!front)
-        for (int a = 0; a < 3; ++a) nn[a] = -nn[a];
-      const u4 r = pcg4d(pix, sample, (uint32_t)(depth + 1), k.seed32);
-      float sd[3];
-      bool scattered = true;
-      if (sc.kind[b] == RT_LAMBERTIAN) {
-        float u[3];
-        unit_vec(unif(r.x), unif(r.y), u[0], u[1], u[2]);
-        for (int a = 0; a < 3; ++a) sd[a] = nn[a] + u[a];
-        const float eps = 1e-8f;
-        if (std::fabs(sd[0]) < eps && std::fabs(sd[1]) < eps && std::fabs(sd[2]) < eps)
-          for (int a = 0; a < 3; ++a) sd[a] = nn[a];
+      const size_t b = (size_t)st.best;
+      const bool near = st.near;
+      bool scattered = st.scattered;
+      if (sc.kind[b] == RT_LAMBERTIAN || sc.kind[b] == RT_METAL) {  // attenuation = albedo; a dielectric's is 1
         th[0] *= sc.ar[b];
         th[1] *= sc.ag[b];
         th[2] *= sc.ab[b];
-      } else if (sc.kind[b] == RT_METAL) {
-        const float kk = -2.0f * dot3(d[0], d[1], d[2], nn[0], nn[1], nn[2]);
-        float rf[3], u[3];
-        for (int a = 0; a < 3; ++a) rf[a] = fmaf_(kk, nn[a], d[a]);
-        unit_vec(unif(r.x), unif(r.y), u[0], u[1], u[2]);
-        float fz = sc.param[b];
-        if (!k.metal_unit) fz *= ball_radius(r);
-        for (int a = 0; a < 3; ++a) sd[a] = fmaf_(fz, u[a], rf[a]);
-        scattered = dot3(sd[0], sd[1], sd[2], nn[0], nn[1], nn[2]) > 0.0f;
-        th[0] *= sc.ar[b];
-        th[1] *= sc.ag[b];
-        th[2] *= sc.ab[b];
-      } else {
-        const float ratio = front ? sc.inv_param[b] : sc.param[b];
-        const float cos_t = std::fmin(-dot3(d[0], d[1], d[2], nn[0], nn[1], nn[2]), 1.0f);
-        // ratio sin > 1 (material.h:64), squared (the kernel's form)
-        const bool cannot = (ratio * ratio) * fmaf_(-cos_t, cos_t, 1.0f) > 1.0f;
-        const float r0 = sc.r0[b];  // ((1-ior)/(1+ior))^2, same for ior and 1/ior
-        const float x = 1.0f - cos_t;
-        const float x2 = x * x;
-        const float refl = fmaf_(1.0f - r0, x2 * x2 * x, r0);
-        if (cannot || refl > unif(r.x)) {
-          const float kk = -2.0f * dot3(d[0], d[1], d[2], nn[0], nn[1], nn[2]);
-          for (int a = 0; a < 3; ++a) sd[a] = fmaf_(kk, nn[a], d[a]);
-        } else {
-          float q[3];
-          for (int a = 0; a < 3; ++a) q[a] = ratio * fmaf_(cos_t, nn[a], d[a]);
-          const float m = -sqrt_k(std::fabs(1.0f - dot3(q[0], q[1], q[2], q[0], q[1], q[2])));
-          for (int a = 0; a < 3; ++a) sd[a] = fmaf_(m, nn[a], q[a]);
-        }
       }
       // the opaque-inside rule: a sealed lambertian
       // sphere hit at its exiting root ends the path (in the reference's
@@ -721,7 +772,7 @@ unsigned long long kernel_pixel(const kctx &k, int col, int grow, float acc[3]) 
           g_ev[e][0] = (long long)b;
           g_ev[e][1] = prev_best;
           g_ev[e][2] = depth;
-          g_ev[e][3] = (long long)(tmin * 1e6f);
+          g_ev[e][3] = (long long)(ray.tmin * 1e6f);
         }
       }
       prev_best = (long)b;
@@ -733,11 +784,11 @@ unsigned long long kernel_pixel(const kctx &k, int col, int grow, float acc[3]) 
       if (scattered && depth >= k.p->max_depth) g_kcapped.fetch_add(1, std::memory_order_relaxed);
       if (!scattered || depth >= k.p->max_depth) break;
       for (int a = 0; a < 3; ++a) {
-        o[a] = p[a];
-        d[a] = sd[a];
+        ray.o[a] = st.p[a];
+        ray.d[a] = st.sd[a];
       }
-      origin_sphere = (long)b;
-      tmin = tmin_of(k.tmin_world, normalize3(d[0], d[1], d[2]));
+      ray.origin_sphere = (long)b;
+      ray.tmin = tmin_of(k.tmin_world, normalize3(ray.d[0], ray.d[1], ray.d[2]));
     }
   }
   for (int a = 0; a < 3; ++a) acc[a] = (wide ? (float)q[a] : (float)(uint32_t)q[a]) * qinv;
@@ -746,6 +797,128 @@ unsigned long long kernel_pixel(const kctx &k, int col, int grow, float acc[3]) 
     for (int a = 0; a < 3; ++a) e[a] = ex[a];
   }
   return segs;
+}
+
+// ---------------------------------------------------------------------
+// The chain restatement (rto_kernel_terminals): one sample's specular chain as
+// include/rt_guides.h specifies it, on kernel_step.  The sample is the
+// render's, segment by segment; a lambertian hit is the terminal, a metal goes
+// on iff it scattered and its clamped fuzz is <= max_fuzz, a dielectric always
+// does, and the chain stops after max_bounces bounces.  A chain that then
+// misses everything escaped: the terminal stays the last counted hit.  thr is
+// the running product of the albedos (1 for a dielectric), held at 2^100 after
+// every multiply in every scene; depth the sum over the counted hits of
+// walked + t, walked collecting the scan roots of first-arm skips since the
+// last counted hit.  A skip normalises the direction again and keeps t_min --
+// but for keep_dir (RTO_TERM_KEEP_DIR), under which a camera ray's skip keeps
+// the direction's bits: rt_aov's form (include/rt_aov.h).  rt_params.max_depth
+// is not read.  trail (may be null): the first kTrail counted hits' spheres.
+constexpr int kTrail = 4;
+void chain_sample(const kctx &k, int col, int grow, uint32_t sample, int max_bounces, float max_fuzz, bool keep_dir,
+                  rto_terminal &out, int32_t *trail) {
+  const kscene &sc = *k.sc;
+  const uint32_t pix = (uint32_t)grow * (uint32_t)k.p->width + (uint32_t)col;
+  kray ray;
+  ray.tmin = camera_ray(k, pix, col, grow, sample, ray.o, ray.d);
+  ray.origin_sphere = -1;
+  float thr[3] = {1.0f, 1.0f, 1.0f};
+  int depth = 0;         // counted hits so far
+  uint32_t nb = 0;       // bounces followed
+  float walked = 0.0f;   // distance to the current origin since the last counted hit
+  float total = 0.0f;    // length walked to the last counted hit
+  uint32_t events = 0, escaped = 0;
+  for (;;) {
+    kstep st;
+    const int what = kernel_step(k, ray, pix, sample, depth, false, st);
+    if (what == KSTEP_MISS) {
+      escaped = ray.origin_sphere >= 0 ? 1u : 0u;
+      break;
+    }
+    if (what == KSTEP_SKIP) {  // not a segment, not a bounce
+      events |= st.arm == 1 ? RTO_EV_SKIP_TMIN : RTO_EV_SKIP_EXIT;
+      if (st.arm == 1) walked += st.tmax;
+      if (!(keep_dir && ray.origin_sphere < 0)) normalize3(ray.d[0], ray.d[1], ray.d[2]);
+      continue;
+    }
+    const size_t b = (size_t)st.best;
+    const uint32_t kind = sc.kind[b];
+    bool cont = false;
+    if (kind == RT_METAL) {
+      if (!st.scattered) events |= RTO_EV_ABSORBED;
+      cont = st.scattered && sc.param[b] <= max_fuzz;
+    } else if (kind != RT_LAMBERTIAN) {
+      cont = true;
+      events |= st.diel == KDIEL_REFRACT ? RTO_EV_REFRACT : st.diel == KDIEL_TIR ? RTO_EV_TIR : RTO_EV_SCHLICK;
+    }
+    if (sc.radius[b] < 0.0f) events |= RTO_EV_NEG_RADIUS;
+    const bool glass = kind != RT_LAMBERTIAN && kind != RT_METAL;
+    const float alb[3] = {glass ? 1.0f : sc.ar[b], glass ? 1.0f : sc.ag[b], glass ? 1.0f : sc.ab[b]};
+    for (int a = 0; a < 3; ++a) {
+      const float x = thr[a] * alb[a];
+      if (x > 0x1p100f) events |= RTO_EV_CLAMP;
+      thr[a] = std::fmin(x, 0x1p100f);
+    }
+    if (trail && depth < kTrail) trail[depth] = (int32_t)b;
+    ++depth;
+    total += walked + st.t;
+    walked = 0.0f;
+    out.sphere = (int32_t)b;
+    for (int a = 0; a < 3; ++a) {
+      out.P[a] = st.p[a];
+      out.N[a] = st.nn[a];
+    }
+    ray.origin_sphere = (long)b;
+    if (!(cont && (int)nb < max_bounces)) {
+      if (cont) events |= RTO_EV_CAP;
+      break;  // the terminal
+    }
+    ++nb;
+    if (kind == RT_METAL && sc.param[b] > 0.0f) events |= RTO_EV_FUZZY;
+    for (int a = 0; a < 3; ++a) {
+      ray.o[a] = st.p[a];
+      ray.d[a] = st.sd[a];
+    }
+    ray.tmin = tmin_of(false, normalize3(ray.d[0], ray.d[1], ray.d[2]));
+  }
+  out.events = events;  // of a miss too: what its primary ray met on the way out
+  if (out.sphere < 0) return;
+  out.depth = total;
+  for (int a = 0; a < 3; ++a) out.thr[a] = thr[a];
+  out.bounces = nb;
+  out.escaped = escaped;
+}
+
+// fn(i, col, grow) for every pixel i = local_row * W + col of the local frame
+// (grow: its row in the whole frame, -1 on a padding row), on `threads`
+// threads (< 1: the machine's, at most 16 and OMP_NUM_THREADS).  The same pool
+// and band-to-row mapping as rto_kernel_render_exact and rto_gpuref_render
+// carry inline: those two are left as they were so that the render entry
+// points (smoke() and the goldens hang on them) do not change with the chain
+// restatement; moving them onto this is a follow-up.
+template <class Fn>
+void for_local_pixels(const rt_params *p, int threads, Fn fn) {
+  if (threads < 1) {
+    threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    if (const char *e = std::getenv("OMP_NUM_THREADS")) {
+      const int k = std::atoi(e);
+      if (k >= 1) threads = std::min(threads, k);
+    }
+  }
+  const long long n_px = (long long)p->local_rows * p->width;
+  std::atomic<long long> next{0};
+  auto worker = [&]() {
+    for (long long i0; (i0 = next.fetch_add(64)) < n_px;)
+      for (long long i = i0; i < std::min(n_px, i0 + 64); ++i) {
+        const int lr = (int)(i / p->width), col = (int)(i % p->width);
+        const int band = lr / p->row_block;
+        const int grow = (band * p->band_stride + p->band_offset) * p->row_block + lr % p->row_block;
+        fn((size_t)i, col, grow < p->height ? grow : -1);
+      }
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < threads; ++t) pool.emplace_back(worker);
+  worker();
+  for (auto &t : pool) t.join();
 }
 
 // ---------------------------------------------------------------------
@@ -1296,6 +1469,35 @@ int rto_kernel_render_exact(const rt_scene_view *scene, const rt_camera *cam, co
 int rto_kernel_render(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p,
                       float *out, unsigned long long *segments, int threads) {
   return rto_kernel_render_exact(scene, cam, p, out, nullptr, 0, segments, threads);
+}
+
+int rto_kernel_terminals_trail(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, int max_bounces,
+                               float max_fuzz, int opts, rto_terminal *out, int32_t *trail, int threads) {
+  if (!scene || !cam || !p || !out || p->width < 1 || p->height < 1 || p->row_block < 1 ||
+      p->band_stride < 1 || p->local_rows < 0 || p->spp < 0 || p->spp >= (1 << 24) || max_bounces < -1 ||
+      max_bounces > 64 || !(max_fuzz >= 0.0f) || (opts & ~RTO_TERM_KEEP_DIR))
+    return -1;
+  const kscene sc = make_kscene(*scene);
+  const kctx k{&sc, cam, p, (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u),
+               (p->flags & RT_FLAG_OPEN_INTERVAL) != 0, (p->flags & RT_FLAG_METAL_UNIT_VECTOR) != 0};
+  const bool keep_dir = (opts & RTO_TERM_KEEP_DIR) != 0;
+  const size_t spp = (size_t)p->spp;
+  for_local_pixels(p, threads, [&](size_t i, int col, int grow) {
+    for (size_t s = 0; s < spp; ++s) {
+      rto_terminal &t = out[i * spp + s];
+      std::memset(&t, 0, sizeof t);
+      t.sphere = -1;
+      int32_t *tr = trail ? trail + kTrail * (i * spp + s) : nullptr;
+      for (int j = 0; tr && j < kTrail; ++j) tr[j] = -1;
+      if (grow >= 0) chain_sample(k, col, grow, (uint32_t)s, std::max(max_bounces, 0), max_fuzz, keep_dir, t, tr);
+    }
+  });
+  return 0;
+}
+
+int rto_kernel_terminals(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, int max_bounces,
+                         float max_fuzz, int opts, rto_terminal *out, int threads) {
+  return rto_kernel_terminals_trail(scene, cam, p, max_bounces, max_fuzz, opts, out, nullptr, threads);
 }
 
 int rto_gpuref_render(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, int mode,

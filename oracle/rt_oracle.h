@@ -70,6 +70,60 @@ enum { RTO_OPT_NO_DITHER = 1, RTO_OPT_TMIN_WORLD = 2, RTO_OPT_NO_SEALED = 4, RTO
 int rto_kernel_render_exact(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p,
                             float *out, double *exact, int opts, unsigned long long *segments,
                             int threads);
+/* The chain restatement: for every sample of every pixel of the local frame,
+ * the record the specular chain of include/rt_guides.h ends with -- the judge
+ * of rt_aov, rt_guides and rt_route (tests/features_ref.py restates their
+ * sums and the vote on these records; tests/test_features_oracle*.py).  It
+ * runs on the very step function the render restatement runs on (closest hit,
+ * refined root, both arms of the spurious-root rule, hit point, face rule and
+ * normal, metal and dielectric scatter), so it shares no code with the
+ * product's csrc/rt_chain.h and rt_trace_pass.h.
+ *   Chain: a lambertian hit is the terminal; a metal goes on iff it scattered
+ * and its fuzz (clamped to 1) is <= max_fuzz; a dielectric always goes on; at
+ * most max_bounces bounces are followed (-1 = 0 = follow nothing, up to 64).
+ * A chain that then misses everything has escaped = 1 and keeps its last
+ * counted hit as the terminal.  thr is the running fp32 product of the albedos
+ * on the path from 1 (a dielectric's is 1), fmin(., 2^100) after every
+ * multiply in every scene.  depth is the sum, from +0 in path order, of
+ * walked + t over the counted hits: walked collects the scan roots of
+ * first-arm skips since the last counted hit.  A skip normalises the
+ * direction again and keeps t_min.  rt_params.max_depth is not read; flags
+ * give the interval and the metal's fuzz form as in a render.
+ *   opts RTO_TERM_KEEP_DIR: a camera ray's skip keeps the direction's bits
+ * instead (rt_aov's form, include/rt_aov.h); with it and max_bounces = -1 the
+ * records are rt_aov's samples, without it rt_guides' at -1.
+ *   out: [local_rows][width][spp] records, banded as rto_kernel_render's rows;
+ * a padding row's records, and a sample whose primary ray missed, have sphere
+ * = -1 and zeros (events excepted).  events: what the sample met on its way,
+ * RTO_EV_* bits, for the tests' coverage conditions.
+ *   Returns -1 for a bad argument (max_bounces outside [-1, 64], a NaN or
+ * negative max_fuzz, an unknown opts bit included). */
+typedef struct {
+  int32_t sphere;            /* original index of the terminal, -1 = the primary ray missed */
+  float depth, P[3], N[3], thr[3];
+  uint32_t bounces, escaped;
+  uint32_t events;
+} rto_terminal;
+enum { RTO_TERM_KEEP_DIR = 1 };
+enum {
+  RTO_EV_SKIP_TMIN = 1,     /* spurious-root skip, arm 1: refined root before t_min */
+  RTO_EV_SKIP_EXIT = 2,     /* arm 2: the exiting root of the sphere the ray starts on */
+  RTO_EV_REFRACT = 4,       /* a refraction taken */
+  RTO_EV_SCHLICK = 8,       /* a reflection chosen by Schlick's reflectance */
+  RTO_EV_TIR = 16,          /* total internal reflection */
+  RTO_EV_ABSORBED = 32,     /* a metal's scatter direction went into the surface */
+  RTO_EV_FUZZY = 64,        /* a metal with fuzz > 0 followed */
+  RTO_EV_NEG_RADIUS = 128,  /* a counted hit on a sphere of negative radius */
+  RTO_EV_CAP = 256,         /* max_bounces reached at a hit that could have gone on */
+  RTO_EV_CLAMP = 512        /* the 2^100 clamp changed the throughput */
+};
+int rto_kernel_terminals(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, int max_bounces,
+                         float max_fuzz, int opts, rto_terminal *out, int threads);
+/* Debug variant: also the spheres of each sample's first 4 counted hits in
+ * path order (trail: [local_rows][width][spp][4] int32, -1 = none; NULL = not
+ * wanted). */
+int rto_kernel_terminals_trail(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, int max_bounces,
+                               float max_fuzz, int opts, rto_terminal *out, int32_t *trail, int threads);
 /* fp64 final scene rows: kind, cx, cy, cz, r, albedo rgb, param (9 doubles). */
 /* src/gpu's own per-sample arithmetic with switches (mode: GREF_* bits in
  * rt_oracle.cc), for attributing differences to the reference CUDA output;

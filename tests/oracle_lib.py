@@ -1,6 +1,10 @@
 """ctypes binding of oracle/librt_oracle.so -- the CHECKER (test infrastructure).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it.
+reference_render* is the fp64 restatement of src/cpu, kernel_render* the fp32
+restatement of the render kernel's algorithm, kernel_terminals the chain
+restatement on the same step function: every sample's terminal record, which
+tests/features_ref.py sums into what rt_aov, rt_guides and rt_route must give.
 """
 import ctypes
 import gzip
@@ -116,6 +120,42 @@ def kernel_render_exact(scene, cam, params, no_dither=False, threads=0):
     the same samples) -> (float32 sums, float64 exact sums, segments).
     no_dither: the sum format without stochastic rounding (truncation)."""
     return _kernel_render_opts(scene, cam, params, RTO_OPT_NO_DITHER if no_dither else 0, True, threads)
+
+
+# rto_terminal (oracle/rt_oracle.h) and its events bits
+TERMINAL = np.dtype([("sphere", np.int32), ("depth", np.float32), ("P", np.float32, 3), ("N", np.float32, 3),
+                     ("thr", np.float32, 3), ("bounces", np.uint32), ("escaped", np.uint32), ("events", np.uint32)])
+RTO_TERM_KEEP_DIR = 1
+EVENTS = {"skip_tmin": 1, "skip_exit": 2, "refract": 4, "schlick": 8, "tir": 16, "absorbed": 32, "fuzzy": 64,
+          "neg_radius": 128, "cap": 256, "clamp": 512}
+TRAIL = 4  # counted hits per sample that kernel_terminals(trail=True) records
+
+
+def kernel_terminals(scene, cam, params, max_bounces=-1, max_fuzz=0.0, keep_dir=False, trail=False, threads=0):
+    """The chain restatement (rto_kernel_terminals): for every sample of every
+    pixel of the local frame the record its specular chain ends with, as
+    include/rt_guides.h specifies the chain -> a structured array of dtype
+    TERMINAL shaped (local_rows, W, spp): sphere (-1 = the primary ray missed,
+    and on padding rows), depth, P, N, thr, bounces, escaped, events (EVENTS
+    bits).  max_bounces -1 or 0 follows nothing (the literal value, not
+    rt_guides_options' 0 = default); params.max_depth is not read.  keep_dir:
+    a camera ray's spurious-root skip keeps the direction's bits (rt_aov's
+    form), so that keep_dir with max_bounces = -1 gives rt_aov's samples.
+    trail: also returns int32 (local_rows, W, spp, TRAIL), the spheres of each
+    sample's first counted hits in path order (-1 = none)."""
+    assert TERMINAL.itemsize == 56
+    L = lib()
+    L.rto_kernel_terminals_trail.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    v = scene.view()
+    shape = (params.local_rows, params.width, params.spp)
+    out = np.zeros(shape, TERMINAL)
+    tr = np.zeros(shape + (TRAIL,), np.int32) if trail else None
+    if out.size:  # spp = 0: no records
+        assert L.rto_kernel_terminals_trail(ctypes.addressof(v), ctypes.addressof(cam), ctypes.addressof(params),
+                                            int(max_bounces), float(max_fuzz), RTO_TERM_KEEP_DIR if keep_dir else 0,
+                                            out.ctypes.data, tr.ctypes.data if trail else None, threads) == 0
+    return (out, tr) if trail else out
 
 
 def trace(scene, cam, params, col, row, sample, max_depth=50):
