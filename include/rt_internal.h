@@ -5,7 +5,8 @@
  * replaces reference code.  These functions exist for the test suite
  * (tests/), the measurement tools (tools/) and host sanitizer runs: the
  * device arithmetic's known-answer vectors, and host-only views of what the
- * BVH / layer-grid builder, the launch planner and the grid fitter decide.
+ * BVH / layer-grid builder, the launch planner and the grid fitter decide,
+ * and views of the pilot schedule (its tile costs and block order).
  * A caller of the reference's render path needs rt.h only.
  */
 #ifndef RTOW_RT_INTERNAL_H
@@ -91,6 +92,37 @@ int rt_internal_grid_scale(rt_context *ctx, double *scale);
  * ball overlaps its ball), else 0.  Writes
  * min(n_out, scene->n) bytes.  For tests. */
 int rt_internal_sealed(const rt_scene_view *scene, uint8_t *out, size_t n_out);
+
+/* The pilot schedule (RT_FLAG_PILOT_SCHEDULE) made visible.  All
+ * three are synchronous, work on host arrays and change no render.  For tests.
+ *
+ * The sort alone on `device`: the launch order the product's device sort
+ * (csrc/rt_sched.hip, the very function pilot_order calls) gives for the tile
+ * costs.  tile_cost holds blocks * 4 entries (block b's tiles at 4 b .. 4 b +
+ * 3), order blocks * units.  A block's cost is the sum of its tiles' (mod
+ * 2^32); blocks in decreasing cost, equal costs in increasing block index;
+ * order[i * units + u] = sorted[i] * units + u.  blocks = 0 or units = 0:
+ * RT_OK, nothing read or written. */
+int rt_internal_block_order_host(int device, const uint32_t *tile_cost, uint32_t blocks, uint32_t units,
+                                 uint32_t *order);
+/* One rt_render of (cam, params) on the context's own stream -- params must
+ * carry RT_FLAG_PILOT_SCHEDULE -- that also shows what its schedule was:
+ * *pilot_ran = 1 if this render ran the pilot (no order was cached for its
+ * frame geometry), and then tile_cost gets the pilot's segment count of each
+ * tile, min(n_cost, blocks * 4) entries, tile t of the local frame (row-major
+ * over its 8x8 tiles) at t, padding tiles 0; *pilot_ran = 0 if the cached
+ * order served, tile_cost untouched.  order gets the first min(n_order,
+ * blocks * units) entries of the order the render's launches read, *n_order_out
+ * its full length (0: the render took launch order -- one block, or nothing
+ * traced).  image (may be NULL): the render's sums, as rt_render's host_rgb. */
+int rt_internal_pilot_schedule(rt_context *ctx, const rt_camera *cam, const rt_params *params, uint32_t *tile_cost,
+                               size_t n_cost, int *pilot_ran, uint32_t *order, size_t n_order, size_t *n_order_out,
+                               float *image);
+/* The block order the context holds, after waiting for the device's work (so
+ * also after rt_render_async on any stream): min(n_order, *n_order_out)
+ * entries; *n_order_out = 0 when it holds none that is valid (no pilot render
+ * yet, or a scene upload since). */
+int rt_internal_context_order(rt_context *ctx, uint32_t *order, size_t n_order, size_t *n_order_out);
 
 #ifdef __cplusplus
 }

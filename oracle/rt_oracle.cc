@@ -1471,6 +1471,22 @@ int rto_kernel_render(const rt_scene_view *scene, const rt_camera *cam, const rt
   return rto_kernel_render_exact(scene, cam, p, out, nullptr, 0, segments, threads);
 }
 
+int rto_kernel_pixel_segments(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, uint32_t *out,
+                              int threads) {
+  if (!scene || !cam || !p || !out || p->width < 1 || p->height < 1 || p->row_block < 1 ||
+      p->band_stride < 1 || p->local_rows < 0 || p->spp < 0 || p->spp >= (1 << 24) ||
+      (p->max_depth > 0 && (uint64_t)p->spp * (uint64_t)p->max_depth >= (1ull << 32)))  // a count fits 32 bits
+    return -1;
+  const kscene sc = make_kscene(*scene);
+  const kctx k{&sc, cam, p, (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u),
+               (p->flags & RT_FLAG_OPEN_INTERVAL) != 0, (p->flags & RT_FLAG_METAL_UNIT_VECTOR) != 0};
+  for_local_pixels(p, threads, [&](size_t i, int col, int grow) {
+    float acc[3];
+    out[i] = grow >= 0 ? (uint32_t)kernel_pixel(k, col, grow, acc) : 0u;
+  });
+  return 0;
+}
+
 int rto_kernel_terminals_trail(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, int max_bounces,
                                float max_fuzz, int opts, rto_terminal *out, int32_t *trail, int threads) {
   if (!scene || !cam || !p || !out || p->width < 1 || p->height < 1 || p->row_block < 1 ||

@@ -70,6 +70,18 @@ enum { RTO_OPT_NO_DITHER = 1, RTO_OPT_TMIN_WORLD = 2, RTO_OPT_NO_SEALED = 4, RTO
 int rto_kernel_render_exact(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p,
                             float *out, double *exact, int opts, unsigned long long *segments,
                             int threads);
+/* The segments (closest-hit queries; a spurious-root skip's repeat is none)
+ * that each pixel's samples [0, p->spp) trace in rto_kernel_render, on the
+ * same step function: out is [local_rows][width] uint32, banded as
+ * rto_kernel_render's rows, 0 on a padding row; their sum is that render's
+ * *segments.  Samples are counter-based -- sample s of a pixel draws from
+ * (pixel, s, seed) alone, and spp enters only the sum format, never a path --
+ * so a pixel's count for samples [0, n) is the same whatever spp, units or
+ * launch split a render traces them under: the judge of the pilot schedule's
+ * tile costs (tests/sched_ref.py).  Returns -1 for a bad argument, spp *
+ * max_depth >= 2^32 included. */
+int rto_kernel_pixel_segments(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, uint32_t *out,
+                              int threads);
 /* The chain restatement: for every sample of every pixel of the local frame,
  * the record the specular chain of include/rt_guides.h ends with -- the judge
  * of rt_aov, rt_guides and rt_route (tests/features_ref.py restates their

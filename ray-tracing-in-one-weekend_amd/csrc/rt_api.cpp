@@ -608,8 +608,17 @@ int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipSt
 // expensive tiles.  Scheduling only: the image does not depend on it.
 // Everything stays on st (the sort runs on the device, rt_sched.hip).
 // kp, v: the render's arguments and variant; *order = the context's block order.
+// sink (rt_internal_pilot_schedule; null otherwise): told whether the pilot
+// ran, and given its tile costs before they are freed.
+struct pilot_sink {
+  uint32_t *tile_cost = nullptr;  // host, n_cost entries
+  size_t n_cost = 0;
+  bool ran = false;   // the pilot ran (no cached order for this geometry)
+  bool used = false;  // the render reads the context's order
+};
 hipError_t pilot_order(rt_context *c, const rt_camera *cam, const rt_params *prm, const rtk::kparams &kp, int v,
-                       unsigned blocks, long long units, hipStream_t st, const uint32_t **order) {
+                       unsigned blocks, long long units, hipStream_t st, const uint32_t **order,
+                       pilot_sink *sink = nullptr) {
   std::vector<uint64_t> key = {(uint64_t)prm->width, (uint64_t)prm->height, (uint64_t)prm->local_rows,
                                (uint64_t)prm->row_block, (uint64_t)prm->band_stride,
                                (uint64_t)prm->band_offset, (uint64_t)units, (uint64_t)(prm->flags & 0x12ffu)};
@@ -642,12 +651,19 @@ hipError_t pilot_order(rt_context *c, const rt_camera *cam, const rt_params *prm
       e = hipMallocAsync((void **)&c->d_order, (size_t)blocks * units * sizeof(uint32_t), st);
     }
     if (e == hipSuccess) e = rt_internal_block_order(d_cost, blocks, (uint32_t)units, c->d_order, st);
+    if (e == hipSuccess && sink) {
+      sink->ran = true;
+      if (sink->tile_cost && sink->n_cost)
+        e = hipMemcpyAsync(sink->tile_cost, d_cost, std::min(sink->n_cost, n_cost) * sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, st);
+    }
     (void)hipFreeAsync(d_cost, st);  // also on error: no leak
     if (e != hipSuccess) return e;
     c->order_n = (size_t)blocks * units;
     c->order_key = key;
   }
   *order = c->d_order;
+  if (sink) sink->used = true;
   return hipSuccess;
 }
 
@@ -683,7 +699,7 @@ hipError_t end_sums(rt_context *c, sum_target t, float *accum_rgb, uint64_t fram
 // recorded behind that work (rt_pass_scope; ADVICE r5: before, only hipFree's
 // implicit device synchronisation covered it).
 int render_enqueue(rt_context *c, const rt_camera *cam, const rt_params *prm, float *accum_rgb, void *stream,
-                   hipEvent_t ev_start) {
+                   hipEvent_t ev_start, pilot_sink *sink = nullptr) {
   rt_pass_scope ps(c, cam, prm, stream);
   if (ps.status != RT_OK) return ps.status;
   rt_frame_setup &fs = ps.fs;
@@ -718,7 +734,7 @@ int render_enqueue(rt_context *c, const rt_camera *cam, const rt_params *prm, fl
   kp.sum_atomic = sums != kSumStore ? 1 : 0;
   const uint64_t frame_floats = (uint64_t)prm->local_rows * (uint64_t)prm->width * 3u;
   if ((prm->flags & RT_FLAG_PILOT_SCHEDULE) && traced && blocks > 1)
-    RT_HIP(pilot_order(c, cam, prm, kp, v, blocks, lp.units, st, &kp.block_order));
+    RT_HIP(pilot_order(c, cam, prm, kp, v, blocks, lp.units, st, &kp.block_order, sink));
   RT_HIP(begin_sums(c, sums, accum_rgb, frame_floats, st, kp));  // (after the pilot, which renders into accum_rgb too)
   while (c->ev_launch.size() < (size_t)launches) {  // one event per bounded launch (the pool only grows)
     hipEvent_t ev = nullptr;
@@ -833,16 +849,21 @@ int rt_collect_stats(rt_context *c, rt_stats *stats) {
   return RT_OK;
 }
 
-int rt_render(rt_context *c, const rt_camera *cam, const rt_params *prm, float *host_rgb,
-              rt_stats *stats) {
-  if (!c || !params_ok(prm) || (!host_rgb && prm->local_rows && prm->width)) return RT_ERR_INVALID;
+}  // extern "C"
+
+namespace {
+
+// rt_render's body; host_rgb null: the frame is not copied back, sink: see
+// pilot_order (rt_internal_pilot_schedule is this render with both)
+int render_sync(rt_context *c, const rt_camera *cam, const rt_params *prm, float *host_rgb, rt_stats *stats,
+                pilot_sink *sink) {
   int st = rt_internal_frame_check(c, cam, prm);
   if (st != RT_OK) return st;
   const size_t nf = 3 * (size_t)prm->width * (size_t)prm->local_rows;
   RT_HIP(hipSetDevice(c->device));
   RT_HIP(c->d_frame.grow(nf));
   // ev0 is recorded right before the render kernel (after a first-frame pilot)
-  st = render_enqueue(c, cam, prm, c->d_frame.p, nullptr, c->ev0);
+  st = render_enqueue(c, cam, prm, c->d_frame.p, nullptr, c->ev0, sink);
   const uint32_t n_launch = std::min<uint32_t>(c->enq_launches, (uint32_t)c->ev_launch.size());
   if (st != RT_OK) return st;
   RT_HIP(hipEventRecord(c->ev1, c->stream));
@@ -851,12 +872,81 @@ int rt_render(rt_context *c, const rt_camera *cam, const rt_params *prm, float *
   RT_HIP(hipEventSynchronize(c->ev1));
   float ms = 0.f;
   RT_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  if (nf) RT_HIP(hipMemcpy(host_rgb, c->d_frame.p, nf * sizeof(float), hipMemcpyDeviceToHost));
+  if (nf && host_rgb) RT_HIP(hipMemcpy(host_rgb, c->d_frame.p, nf * sizeof(float), hipMemcpyDeviceToHost));
   if (stats) {
     st = rt_collect_stats(c, stats);
     if (st != RT_OK) return st;
     stats->kernel_ms = ms;
   }
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render(rt_context *c, const rt_camera *cam, const rt_params *prm, float *host_rgb,
+              rt_stats *stats) {
+  if (!c || !params_ok(prm) || (!host_rgb && prm->local_rows && prm->width)) return RT_ERR_INVALID;
+  return render_sync(c, cam, prm, host_rgb, stats, nullptr);
+}
+
+// The pilot schedule's diagnostics (include/rt_internal.h;
+// tests/test_sched_gpu.py compares them with tests/sched_ref.py on the
+// oracle's per-pixel segment counts).
+int rt_internal_block_order_host(int device, const uint32_t *tile_cost, uint32_t blocks, uint32_t units,
+                                 uint32_t *order) {
+  if (!blocks || !units) return RT_OK;
+  const uint64_t n_cost = (uint64_t)blocks * rtk::kWavesPerBlock, n_order = (uint64_t)blocks * units;
+  if (!tile_cost || !order || n_cost >= (1ull << 32) || n_order >= (1ull << 32)) return RT_ERR_INVALID;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return RT_ERR_NO_DEVICE;
+  RT_HIP(hipSetDevice(device));
+  hipStream_t st = nullptr;
+  RT_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  rt_device_buf<uint32_t> d_cost, d_order;
+  hipError_t e = d_cost.grow(n_cost);
+  if (e == hipSuccess) e = d_order.grow(n_order);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_cost.p, tile_cost, n_cost * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = rt_internal_block_order(d_cost.p, blocks, units, d_order.p, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(order, d_order.p, n_order * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);  // (also after a failure: the copies read the buffers)
+  (void)hipStreamDestroy(st);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail(e);
+  return RT_OK;
+}
+
+int rt_internal_pilot_schedule(rt_context *c, const rt_camera *cam, const rt_params *prm, uint32_t *tile_cost,
+                               size_t n_cost, int *pilot_ran, uint32_t *order, size_t n_order, size_t *n_order_out,
+                               float *image) {
+  if (!c || !params_ok(prm) || !(prm->flags & RT_FLAG_PILOT_SCHEDULE) || !pilot_ran || !n_order_out ||
+      (n_cost && !tile_cost) || (n_order && !order))
+    return RT_ERR_INVALID;
+  *pilot_ran = 0;
+  *n_order_out = 0;
+  pilot_sink sink;
+  sink.tile_cost = tile_cost;
+  sink.n_cost = n_cost;
+  const int r = render_sync(c, cam, prm, image, nullptr, &sink);  // (waits for the stream: the costs have arrived)
+  if (r != RT_OK) return r;
+  *pilot_ran = sink.ran ? 1 : 0;
+  if (!sink.used) return RT_OK;
+  *n_order_out = c->order_n;
+  if (std::min(n_order, c->order_n))
+    RT_HIP(hipMemcpy(order, c->d_order, std::min(n_order, c->order_n) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_internal_context_order(rt_context *c, uint32_t *order, size_t n_order, size_t *n_order_out) {
+  if (!c || !n_order_out || (n_order && !order)) return RT_ERR_INVALID;
+  *n_order_out = 0;
+  RT_HIP(hipSetDevice(c->device));
+  RT_HIP(hipDeviceSynchronize());  // renders on caller streams included
+  if (c->order_key.empty() || !c->d_order) return RT_OK;
+  *n_order_out = c->order_n;
+  if (std::min(n_order, c->order_n))
+    RT_HIP(hipMemcpy(order, c->d_order, std::min(n_order, c->order_n) * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

@@ -771,6 +771,48 @@ class Context:
                               out.ctypes.data, ctypes.byref(st)), "rt_render")
         return out, st
 
+    def pilot_schedule(self, cam, params):
+        """One synchronous render of (cam, params) -- params carries
+        RT_FLAG_PILOT_SCHEDULE -- that also shows its schedule
+        (rt_internal_pilot_schedule): a dict of "image" (the sums, as render's),
+        "pilot_ran" (False: the context's cached order served), "tile_cost"
+        (uint32 [blocks * 4], the pilot's segments per tile of the local frame
+        in row-major tile order; None unless the pilot ran) and "order" (uint32
+        [blocks * units], the block order the launches read; empty when the
+        render took launch order)."""
+        L = lib()
+        L.rt_internal_pilot_schedule.argtypes = [ctypes.c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Params),
+                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int),
+                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                                 ctypes.c_void_p]
+        blocks = frame_blocks(params)
+        cost = np.zeros(blocks * 4, np.uint32)
+        order = np.zeros(blocks * 8, np.uint32)  # (units is at most 8)
+        image = np.zeros((params.local_rows, params.width, 3), np.float32)
+        ran, n = ctypes.c_int(), ctypes.c_size_t()
+        check(L.rt_internal_pilot_schedule(self._h, ctypes.byref(cam), ctypes.byref(params), cost.ctypes.data,
+                                           cost.size, ctypes.byref(ran), order.ctypes.data, order.size,
+                                           ctypes.byref(n), image.ctypes.data), "rt_internal_pilot_schedule")
+        assert n.value <= order.size, n.value
+        return {"image": image, "pilot_ran": bool(ran.value), "tile_cost": cost if ran.value else None,
+                "order": order[:n.value].copy()}
+
+    def block_order(self):
+        """The block order the context holds (rt_internal_context_order), read
+        after the device's work is done, so also after render_async on any
+        stream: uint32 [blocks * units]; empty when it holds none that is
+        valid (no render with RT_FLAG_PILOT_SCHEDULE yet, or an upload since)."""
+        L = lib()
+        L.rt_internal_context_order.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                ctypes.POINTER(ctypes.c_size_t)]
+        n = ctypes.c_size_t()
+        check(L.rt_internal_context_order(self._h, None, 0, ctypes.byref(n)), "rt_internal_context_order")
+        order = np.zeros(n.value, np.uint32)
+        check(L.rt_internal_context_order(self._h, order.ctypes.data, order.size, ctypes.byref(n)),
+              "rt_internal_context_order")
+        assert n.value == order.size
+        return order
+
     def render_async(self, cam, params, dev_ptr, stream=0):
         """Enqueue into a device pointer (e.g. torch tensor.data_ptr()) on a hipStream_t."""
         check(lib().rt_render_async(self._h, ctypes.byref(cam), ctypes.byref(params),
@@ -1159,6 +1201,30 @@ def launch_plan(params, launch_samples=0.0):
     check(lib().rt_internal_launch_plan(ctypes.byref(params), float(launch_samples), out.ctypes.data, out.size),
           "rt_internal_launch_plan")
     return {k: int(x) for k, x in zip(LAUNCH_PLAN_KEYS, out)}
+
+
+def frame_blocks(params):
+    """The render's blocks for `params`: four 8x8 tiles (one wave each) per
+    block over the local frame's tiles in row-major order (csrc/rt_frame.h)."""
+    tiles = -(-params.width // 8) * -(-params.local_rows // 8)
+    return -(-tiles // 4)
+
+
+def block_order_host(tile_cost, blocks, units, device=0):
+    """The pilot schedule's device sort alone (rt_internal_block_order_host),
+    on `device`: tile_cost uint32 [blocks * 4] -> the launch order, uint32
+    [blocks * units]: blocks by decreasing cost (the sum of their four tiles),
+    equal costs in block order, a block's units adjacent."""
+    L = lib()
+    L.rt_internal_block_order_host.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_void_p]
+    cost = np.ascontiguousarray(tile_cost, np.uint32)
+    if cost.shape != (blocks * 4,):
+        raise ValueError(f"tile_cost: shape {cost.shape}, expected ({blocks * 4},)")
+    order = np.zeros(blocks * units, np.uint32)
+    check(L.rt_internal_block_order_host(device, cost.ctypes.data, blocks, units, order.ctypes.data),
+          "rt_internal_block_order_host")
+    return order
 
 
 def write_ppm(path, rgb, binary=False):

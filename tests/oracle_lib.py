@@ -122,6 +122,25 @@ def kernel_render_exact(scene, cam, params, no_dither=False, threads=0):
     return _kernel_render_opts(scene, cam, params, RTO_OPT_NO_DITHER if no_dither else 0, True, threads)
 
 
+def kernel_pixel_segments(scene, cam, params, samples=None, threads=0):
+    """The segments each pixel's samples [0, samples) trace in kernel_render
+    (rto_kernel_pixel_segments; samples None: params.spp) -> uint32 (rows, W),
+    0 on padding rows.  Their sum is kernel_render's segments at that spp.
+    Samples are counter-based: the counts do not depend on params.spp, units
+    or any launch split."""
+    import copy
+    p = copy.copy(params)
+    if samples is not None:
+        p.spp = int(samples)
+    L = lib()
+    L.rto_kernel_pixel_segments.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int]
+    v = scene.view()
+    out = np.zeros((p.local_rows, p.width), np.uint32)
+    assert L.rto_kernel_pixel_segments(ctypes.addressof(v), ctypes.addressof(cam), ctypes.addressof(p),
+                                       out.ctypes.data, threads) == 0
+    return out
+
+
 # rto_terminal (oracle/rt_oracle.h) and its events bits
 TERMINAL = np.dtype([("sphere", np.int32), ("depth", np.float32), ("P", np.float32, 3), ("N", np.float32, 3),
                      ("thr", np.float32, 3), ("bounces", np.uint32), ("escaped", np.uint32), ("events", np.uint32)])
