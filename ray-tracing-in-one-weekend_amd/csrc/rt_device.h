@@ -618,26 +618,32 @@ __device__ __forceinline__ int walk_step(const bvh_node &nd, int node, bool hit,
 
 // one grid item (cx, cz, ks, closed tie key): the leaf test's arithmetic in
 // plain fp32 (NOY fold: the same bits as scan_pairs) and the candidate rule
+// live: the lane's cell holds this item.  The item loops pass true under their
+// own exec mask; the kGridLds chain (grid_walk) runs a stage on every walking
+// lane and passes n > k, so a lane past its cell's end computes on whatever
+// the read returned and can never be a candidate.
+// lm: the wave's mask of live lanes (their ballot; all ones in a loop), so the
+// branch on the wave is one scalar AND of two compare masks.
 template <bool OPEN, bool STATS>
-__device__ __forceinline__ void grid_item(const f4 it, float dx, float dz, const ray_pre &rl, float tmin,
-                                          hit_state &hs, work_ctr &wc) {
+__device__ __forceinline__ void grid_item(const f4 it, bool live, uint64_t lm, float dx, float dz,
+                                          const ray_pre &rl, float tmin, hit_state &hs, work_ctr &wc) {
   if (STATS && RT_COUNT_ITEMS == 1 && lane_now() == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true))) ++wc.box_hits;
   const float h = fmaf(it.y, dz, fmaf(it.x, dx, rl.nk1.x));
   const float g = fmaf(it.y, rl.oz2.x, fmaf(it.x, rl.ox2.x, rl.o2.x));
   const float e = fmaf(h, h, -g);
-  if (STATS && RT_COUNT_ITEMS == 2 && __builtin_amdgcn_ballot_w64(e >= it.z) &&
-      lane_now() == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true)))
-    ++wc.box_hits;
   // it.w holds tie2_of<false>(index); the open interval's is 0xfffffffe - it
   const uint32_t w = __float_as_uint(it.w);
-  const bool c = e >= it.z;
-  LP(kLpItem, true);
-  // a wave-uniform branch; the sequence runs under the item loop's own mask
-  if (__builtin_amdgcn_ballot_w64(c)) {
+  const bool c = live & (e >= it.z);
+  const uint64_t cm = __builtin_amdgcn_ballot_w64(e >= it.z) & lm;
+  if (STATS && RT_COUNT_ITEMS == 2 && cm && lane_now() == __builtin_ctzll(__builtin_amdgcn_ballot_w64(true)))
+    ++wc.box_hits;
+  LP(kLpItem, live);
+  // a wave-uniform branch; the sequence runs under the caller's mask
+  if (cm) {
     LP(kLpGridCand, c);
     candidate<OPEN>(c, h, e - it.z, OPEN ? 0xfffffffeu - w : w, tmin, hs);
   }
-  if (STATS) ++wc.tests;
+  if (STATS) wc.tests += live ? 1u : 0u;
 }
 
 // Per-lane 2-D DDA over the layer grid (layer mode): the lane visits the x-z
@@ -708,10 +714,40 @@ __device__ __forceinline__ void grid_walk(float ox, float oz, float ix, float iz
       lds_f4 *ie = (lds_f4 *)(uintptr_t)((lds_u16 *)(uintptr_t)cell)[1];
       // (both bounds behind one barrier: one wait for the two reads)
       asm volatile("" : "+v"(ip), "+v"(ie));
-      if (ip != ie) do {
-        grid_item<OPEN, STATS>(*ip, dx, dz, rl, tmin, hs, wc);
-        ++ip;
-      } while (ip != ie);
+      // The cell's first kItemChain items as a straight-line chain: stage k
+      // reads ip[k] at an immediate offset and tests it on every walking lane,
+      // masked by n > k -- no per-item pointer step, exit compare or exec-mask
+      // back-edge.  A stage is entered only while some lane has n > k (one
+      // v_cmp and a scalar branch), so the wave runs as many stages as its
+      // busiest lane has items.  A lane with n <= k reads past its cell's end,
+      // at most kItemChain items: still inside the block's grid copy
+      // (grid_lds_bytes keeps that much behind the last item).
+      const uint32_t nb = (uint32_t)(uintptr_t)ie - (uint32_t)(uintptr_t)ip;  // 16 n
+      [&] {
+        f4 it[kItemChain];
+#pragma unroll
+        for (int k = 0; k < kItemChain; ++k) {
+          const bool live = nb > 16u * (uint32_t)k;
+          const uint64_t lm = __builtin_amdgcn_ballot_w64(live);
+          if (!lm) return;
+          // the reads ahead of their stage (their addresses need no clamp)
+          if (RT_ITEM_AHEAD == 0 || (RT_ITEM_AHEAD == 1 && k == 0)) it[k] = ip[k];
+          if (RT_ITEM_AHEAD == 1 && k + 1 < kItemChain) it[k + 1] = ip[k + 1];
+          if (RT_ITEM_AHEAD == 2 && k == 0) {
+#pragma unroll
+            for (int j = 0; j < kItemChain; ++j) it[j] = ip[j];
+          }
+          grid_item<OPEN, STATS>(it[k], live, lm, dx, dz, rl, tmin, hs, wc);
+        }
+        // cells with more items (dense scenes): the pointer loop from ip[kItemChain]
+        if (nb > 16u * (uint32_t)kItemChain) {
+          lds_f4 *iq = ip + kItemChain;
+          do {
+            grid_item<OPEN, STATS>(*iq, true, ~0ull, dx, dz, rl, tmin, hs, wc);
+            ++iq;
+          } while (iq != ie);
+        }
+      }();
     } else {
       uint32_t k, ke;
       if (GP == kGridCells) {
@@ -728,8 +764,8 @@ __device__ __forceinline__ void grid_walk(float ox, float oz, float ix, float iz
       uint32_t ko = k << 4;
       const uint32_t koe = ke << 4;
       if (ko != koe) do {
-        grid_item<OPEN, STATS>(*(const RT_GLOBAL f4 *)((const RT_GLOBAL char *)items + ko), dx, dz, rl, tmin, hs,
-                               wc);
+        grid_item<OPEN, STATS>(*(const RT_GLOBAL f4 *)((const RT_GLOBAL char *)items + ko), true, ~0ull, dx, dz, rl,
+                               tmin, hs, wc);
         ko += 16;
       } while (ko != koe);
     }

@@ -187,10 +187,30 @@ struct kparams {
   float extras_cy;
 };
 
-// LDS bytes of the grid copy of one block
+// kGridLds walk (grid_walk): a cell's first kItemChain items are tested as a
+// straight-line chain at immediate LDS offsets, the rest by the pointer loop.
+// RT_ITEM_AHEAD: how many of the chain's reads are issued before the test
+// they follow (0: each stage reads its own item; 1: the next stage's too; 2:
+// all of them on entry) -- A/B axes of tools/build_variant.sh, DESIGN.md 8.
+#ifndef RT_ITEM_CHAIN
+#define RT_ITEM_CHAIN 4
+#endif
+#ifndef RT_ITEM_AHEAD
+#define RT_ITEM_AHEAD 2
+#endif
+constexpr int kItemChain = RT_ITEM_CHAIN;
+static_assert(kItemChain >= 1 && kItemChain <= 15, "a cell holds at most 15 items");
+
+// LDS bytes of the grid copy of one block.  kGridLds: a chain stage runs on
+// every walking lane, so a lane in an empty cell reads up to kItemChain items
+// past the last one; at least that many bytes follow the items: the cell
+// starts (32 cells or more cover a chain of 4: no such scene's size changes)
+// or padding.
 __host__ __device__ constexpr size_t grid_lds_bytes(int placement, long long n_items, long long n_cells) {
-  return placement == kGridLds ? (size_t)n_items * 16u + ((size_t)(n_cells + 1) * 2u + 15u) / 16u * 16u
-         : placement == kGridCells ? ((size_t)(n_cells + 1) * 2u + 15u) / 16u * 16u
+  const size_t cells = ((size_t)(n_cells + 1) * 2u + 15u) / 16u * 16u;
+  const size_t over = (size_t)kItemChain * 16u;
+  return placement == kGridLds ? (size_t)n_items * 16u + (cells > over ? cells : over)
+         : placement == kGridCells ? cells
                                    : 0u;
 }
 // LDS budget of the grid copy: with render_kernel's static LDS (the tiles'
