@@ -51,11 +51,17 @@ int rt_device_kat(int device, int kind, const double *in, size_t n_cases, double
  *     coaxial spheres share (float32; 0 without RT_EXTRAS_COAXIAL)
  *  20..35 the first 16 extras slots in scan order: 1 + original index (the
  *     slot's tie key), 0 = padding or no such slot
+ *  36..42 the layer grid's geometry as the kernel gets it, each the bits of a
+ *     float32 (0 without a grid): 36 grid_xi, 37 grid_zi (the listed region's
+ *     low corner), 38 grid_g (the cell side), 39 grid_x1, 40 grid_z1 (its high
+ *     corner), 41 grid_x0, 42 grid_z0 (the stored cells' origin, one ring
+ *     cell before the listed region: the walk's border between stored columns
+ *     k - 1 and k is fmaf((float)k, grid_g, grid_x0), likewise in z)
  * Classes compare bit patterns; only +0 is zero:
  *   RT_EXTRAS_AXIAL    slot 0 has cx = cz = +0
  *   RT_EXTRAS_COAXIAL  the group's other spheres share one cy and have cz = +0
  * For tests and sanitizer runs. */
-#define RT_ACCEL_INFO_N 36
+#define RT_ACCEL_INFO_N 43
 enum { RT_EXTRAS_AXIAL = 1, RT_EXTRAS_COAXIAL = 2 };
 int rt_internal_accel_info(const rt_scene_view *scene, int grid_placement, double grid_scale, uint64_t *out,
                            size_t n_out);

@@ -1516,6 +1516,22 @@ int rto_kernel_terminals(const rt_scene_view *scene, const rt_camera *cam, const
   return rto_kernel_terminals_trail(scene, cam, p, max_bounces, max_fuzz, opts, out, nullptr, threads);
 }
 
+int rto_camera_origins(const rt_camera *cam, const rt_params *p, float *out, int threads) {
+  if (!cam || !p || !out || p->width < 1 || p->height < 1 || p->row_block < 1 || p->band_stride < 1 ||
+      p->local_rows < 0 || p->spp < 0 || p->spp >= (1 << 24))
+    return -1;
+  const kctx k{nullptr, cam, p, (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u), false, false};
+  const size_t spp = (size_t)p->spp;
+  for_local_pixels(p, threads, [&](size_t i, int col, int grow) {
+    for (size_t s = 0; s < spp; ++s) {
+      float *o = out + 3 * (i * spp + s), d[3];
+      o[0] = o[1] = o[2] = 0.0f;
+      if (grow >= 0) camera_ray(k, (uint32_t)grow * (uint32_t)p->width + (uint32_t)col, col, grow, (uint32_t)s, o, d);
+    }
+  });
+  return 0;
+}
+
 int rto_gpuref_render(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, int mode,
                       float *out, unsigned long long *segments, int threads) {
   if (!scene || !cam || !p || !out || p->width < 1 || p->height < 1 || p->row_block < 1 ||

@@ -136,6 +136,10 @@ int rto_kernel_terminals(const rt_scene_view *scene, const rt_camera *cam, const
  * wanted). */
 int rto_kernel_terminals_trail(const rt_scene_view *scene, const rt_camera *cam, const rt_params *p, int max_bounces,
                                float max_fuzz, int opts, rto_terminal *out, int32_t *trail, int threads);
+/* The origin of every sample's camera ray, as the render restatement draws it
+ * (the eye, or with a lens fma(ddy, lens_v, fma(ddx, lens_u, eye))):
+ * out[local_rows][width][spp][3] float, zeros on padding rows. */
+int rto_camera_origins(const rt_camera *cam, const rt_params *p, float *out, int threads);
 /* fp64 final scene rows: kind, cx, cy, cz, r, albedo rgb, param (9 doubles). */
 /* src/gpu's own per-sample arithmetic with switches (mode: GREF_* bits in
  * rt_oracle.cc), for attributing differences to the reference CUDA output;

@@ -1018,6 +1018,13 @@ int rt_internal_accel_info(const rt_scene_view *s, int grid_placement, double gr
   v[19] = cy_bits;
   for (size_t k = 0; a.layer_mode && k < 16 && k < 2 * (size_t)a.n_extra_pairs; ++k)
     v[20 + k] = (uint64_t)(a.slots[2 * (size_t)a.extra_pair0 + k] + 1);
+  // the grid's geometry as the kernel gets it (grid_kparams): float32 bits
+  const float geom[7] = {g.xi, g.zi, g.g, g.x1, g.z1, g.x0, g.z0};
+  for (size_t k = 0; cells && k < 7; ++k) {
+    uint32_t bits;
+    std::memcpy(&bits, &geom[k], sizeof bits);
+    v[36 + k] = bits;
+  }
   std::memcpy(out, v, std::min<size_t>(n_out, RT_ACCEL_INFO_N) * sizeof(uint64_t));
   return RT_OK;
 }

@@ -1130,17 +1130,24 @@ ACCEL_INFO_KEYS = ("nodes_per_order", "bvh_slots", "layer_mode", "extra_pair0", 
                    "grid_nx", "grid_nz", "grid_items", "grid_lds_bytes", "grid_fits_lds",
                    "max_items_per_cell", "grid_starts_ok", "grid_ring_empty", "oref_milli",
                    "layer_slots", "listed_cells", "grid_placement", "grid_scale_milli")
+# rt_internal_accel_info's values 36..42: the layer grid's geometry as the kernel gets it (float32 bits)
+ACCEL_INFO_GRID_KEYS = ("grid_xi", "grid_zi", "grid_g", "grid_x1", "grid_z1", "grid_x0", "grid_z0")
+ACCEL_INFO_N = 43  # RT_ACCEL_INFO_N
 
 
 def accel_info(scene, grid_mode="auto", grid_scale=0.0):
     """What rt_scene_upload would build for `scene` with those grid options,
     computed on the host (rt_internal_accel_info; no device): a dict of
-    ACCEL_INFO_KEYS."""
+    ACCEL_INFO_KEYS (ints) and ACCEL_INFO_GRID_KEYS (numpy float32, the very
+    bits the kernel gets; 0 without a grid)."""
     v = scene.view()
-    out = np.zeros(len(ACCEL_INFO_KEYS), np.uint64)
+    out = np.zeros(ACCEL_INFO_N, np.uint64)
     check(lib().rt_internal_accel_info(ctypes.byref(v), GRID_PLACEMENTS[grid_mode], float(grid_scale),
                                        out.ctypes.data, out.size), "rt_internal_accel_info")
-    return {k: int(x) for k, x in zip(ACCEL_INFO_KEYS, out)}
+    info = {k: int(x) for k, x in zip(ACCEL_INFO_KEYS, out)}
+    geom = out[36:36 + len(ACCEL_INFO_GRID_KEYS)].astype(np.uint32).view(np.float32)
+    info.update(zip(ACCEL_INFO_GRID_KEYS, geom))
+    return info
 
 
 def grid_fit(scene, cam, width, height, phase=(0.0, 0.0)):

@@ -177,6 +177,18 @@ def kernel_terminals(scene, cam, params, max_bounces=-1, max_fuzz=0.0, keep_dir=
     return (out, tr) if trail else out
 
 
+def camera_origins(cam, params, threads=0):
+    """The origin of every sample's camera ray as the render restatement draws
+    it (rto_camera_origins) -> float32 (local_rows, W, spp, 3), zeros on
+    padding rows."""
+    L = lib()
+    L.rto_camera_origins.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    out = np.zeros((params.local_rows, params.width, params.spp, 3), np.float32)
+    if out.size:
+        assert L.rto_camera_origins(ctypes.addressof(cam), ctypes.addressof(params), out.ctypes.data, threads) == 0
+    return out
+
+
 def trace(scene, cam, params, col, row, sample, max_depth=50):
     """Print one sample's segments and candidate spheres (debug tooling)."""
     import copy

@@ -12,30 +12,13 @@ import numpy as np
 import pytest
 
 from oracle_lib import kernel_render
+from ray_fans import crowd
 
 pytestmark = pytest.mark.gpu
 
 K = 4  # RT_ITEM_CHAIN of the product build (csrc/rt_layout.h)
 MODES = ("lds", "cells", "global")
 INTERVALS = {"closed": 0, "open": 1}  # RT_FLAG_OPEN_INTERVAL
-
-
-def crowd(rtow, cx, cz, radius, seed):
-    """The ground and len(cx) small spheres of one radius resting on it (a
-    layer scene: the construction of test_dense_layer_grid_build_paths)."""
-    rng = np.random.default_rng(seed)
-    f32 = np.float32
-    n_small = len(cx)
-    kind = np.array([0] + [int(k) for k in rng.integers(0, 3, n_small)], np.uint32)
-    return dataclasses.replace(
-        rtow.final_scene(),
-        cx=np.array([0.0] + list(cx), f32),
-        cy=np.array([-1000.0] + [radius] * n_small, f32),
-        cz=np.array([0.0] + list(cz), f32),
-        radius=np.array([1000.0] + [radius] * n_small, f32),
-        kind=kind,
-        albedo=rng.uniform(0.2, 0.9, (n_small + 1, 3)).astype(f32),
-        param=np.where(kind == 2, 1.5, 0.3).astype(f32))
 
 
 # 80 spheres thrown into a square of half side `half`, and the cell scale at
@@ -105,8 +88,10 @@ def test_dense_layers_fill_the_chain_and_the_loop(rtow, gpu_ctx, most, interval)
 
 def corridor(rtow):
     """Two crowds either side of an empty strip |x| < 1.4, and a camera inside
-    the layer's y-range looking straight down the strip (direction x exactly 0
-    in the centre column): its rays cross empty cells only (n = 0)."""
+    the layer's y-range looking straight down the strip (direction x nearly 0
+    around the centre column; the pixel jitter keeps it from being exactly 0,
+    which test_ray_fans_gpu.py's fans cover): its rays cross empty cells only
+    (n = 0)."""
     rng = np.random.default_rng(7)
     side = rng.integers(0, 2, 80) * 2 - 1
     scene = crowd(rtow, side * rng.uniform(1.5, 3.0, 80), rng.uniform(-3.0, 3.0, 80), 0.1, 8)

@@ -49,6 +49,9 @@ static void accel(const rt_scene_view &v, bool expect_layer) {
       CHECK(rt_internal_accel_info(&v, place, scale, info, RT_ACCEL_INFO_N) == RT_OK);
       CHECK((info[2] != 0) == expect_layer);
       if (info[7]) CHECK(info[11] == 1 && info[12] == 1 && info[10] <= 15 && info[16] >= 1);
+      // values 36..42: the grid's geometry as float32 bits, zeros without a grid
+      for (int k = 36; k < RT_ACCEL_INFO_N; ++k) CHECK(info[k] <= 0xffffffffull && (info[7] || info[k] == 0));
+      CHECK((info[38] != 0) == (info[5] != 0));  // a cell side iff stored cells
     }
   uint64_t two[2];
   CHECK(rt_internal_accel_info(&v, 0, 0.0, two, 2) == RT_OK);  // a short buffer is filled, no more
