@@ -599,6 +599,30 @@ int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipSt
   return RT_OK;
 }
 
+// frame_begin without a camera (rt_internal_scene_begin: librtow_trace.so's
+// pass over the caller's rays): the scene's and the current grid's kernel
+// arguments, the camera and frame fields left zero; no frame geometry, so no
+// refit -- the pass walks the grid the context holds.
+int scene_begin(rt_context *c, uint32_t flags, hipStream_t st, rt_frame_setup &fs) {
+  {
+    const int r = pass_begin(c, st, fs);
+    if (r != RT_OK) return r;
+  }
+  rtk::kparams &kp = fs.kp;
+  const scene_state &s = c->sc;
+  scene_kparams(s, kp);
+  grid_kparams(s, kp);
+  kp.flags = flags;
+  // refit_grid leaves grid.scale = NaN when a copy into the grid's buffers
+  // failed: they hold neither grid until the next grid render refits, and
+  // nothing refits here, so the pass walks the layer BVH (the same bits)
+  const bool grid = s.d_grid_cells.p && !(flags & RT_FLAG_LAYER_BVH) && !std::isnan(s.grid.scale);
+  fs.grid = grid ? 1 : 0;
+  fs.placement = grid ? s.grid_placement : rtk::kGridGlobal;
+  fs.lds_bytes = rtk::grid_lds_bytes(fs.placement, kp.grid_n_items, kp.grid_n_cells);
+  return RT_OK;
+}
+
 // Expensive tiles first (RT_FLAG_PILOT_SCHEDULE): a 4-spp pilot (same
 // geometry, one wave per tile, the instrumented build that reports each
 // tile's segments) runs once per frame geometry; blocks are then launched
@@ -782,6 +806,18 @@ int rt_internal_frame_begin(rt_context *c, const rt_camera *cam, const rt_params
   const int r = rt_internal_frame_check(c, cam, prm);
   if (r != RT_OK) return r;
   return frame_begin(c, cam, prm, stream ? (hipStream_t)stream : c->stream, *out);
+}
+
+int rt_internal_scene_check(const rt_context *c) {
+  if (!c) return RT_ERR_INVALID;
+  return c->sc.d_geom.p ? RT_OK : RT_ERR_NO_SCENE;
+}
+
+int rt_internal_scene_begin(rt_context *c, uint32_t flags, void *stream, rt_frame_setup *out) {
+  if (!out) return RT_ERR_INVALID;
+  const int r = rt_internal_scene_check(c);
+  if (r != RT_OK) return r;
+  return scene_begin(c, flags, stream ? (hipStream_t)stream : c->stream, *out);
 }
 
 int rt_internal_pass_begin(rt_context *c, void *stream, rt_frame_setup *out) {

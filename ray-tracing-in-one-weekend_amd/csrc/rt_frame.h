@@ -3,7 +3,8 @@
 // render in rt_api.cpp, the first-hit feature pass in rt_aov.hip /
 // librtow_aov.so, the chain-following ones in rt_guides.hip /
 // librtow_guides.so and rt_route.hip / librtow_route.so) begins with
-// rt_internal_frame_begin; an image-space pass
+// rt_internal_frame_begin, the pass over the caller's own rays (rt_trace.hip /
+// librtow_trace.so) with rt_internal_scene_begin; an image-space pass
 // that only shares the context's ordering (the denoiser in rt_denoise.hip /
 // librtow_denoise.so, temporal accumulation in rt_temporal.hip /
 // librtow_temporal.so, the resolve in rt_resolve.hip / librtow_resolve.so,
@@ -57,6 +58,18 @@ int rt_internal_frame_check(const rt_context *ctx, const rt_camera *cam, const r
 int rt_internal_frame_begin(rt_context *ctx, const rt_camera *cam, const rt_params *params, void *stream,
                             rt_frame_setup *out);
 
+// rt_internal_frame_begin without a camera, for a pass that traces the
+// caller's own rays (rt_trace.hip / librtow_trace.so): hipSetDevice, the wait
+// on the previous pass, the walk and grid placement for `flags` over the grid
+// the context currently holds (the builder's or the last frame's fit: without
+// a frame geometry there is no RT_OPT_GRID_FIT refit) and the scene's and the
+// grid's kernel arguments; the camera and frame fields of out->kp stay zero.
+// RT_ERR_INVALID for a NULL argument, RT_ERR_NO_SCENE before rt_scene_upload
+// (rt_internal_scene_check: the same two without a HIP call).  Ends with
+// rt_internal_frame_end like the others.
+int rt_internal_scene_check(const rt_context *ctx);
+int rt_internal_scene_begin(rt_context *ctx, uint32_t flags, void *stream, rt_frame_setup *out);
+
 // The same for a pass that reads no scene (the image-space passes): hipSetDevice
 // and the wait on the context's previous pass; of *out only stream, ev0 and
 // ev1 are set, the rest is zero.  RT_ERR_INVALID for a NULL argument, no HIP
@@ -109,8 +122,23 @@ int rt_sample_ranges(int spp, long long per, F f) {
   return RT_OK;
 }
 
+// The flags of a pass over the scene without a camera (rt_pass_scope's third
+// constructor: rt_internal_scene_begin)
+struct rt_scene_flags {
+  uint32_t flags;
+};
+
+// How rt_trace cuts a batch of n rays into launches: ascending ranges of
+// launch_samples (RT_OPT_LAUNCH_SAMPLES) rays at most, at least one; at most
+// kMaxLaunches launches.  No HIP.
+inline unsigned long long rt_rays_per_launch(unsigned long long n, double launch_samples) {
+  const double per = std::floor(std::min(std::max(launch_samples, 1.0), (double)std::max(n, 1ULL)));
+  return std::max((unsigned long long)per, (n + rtk::kMaxLaunches - 1) / rtk::kMaxLaunches);
+}
+
 // One pass on a stream: begins it (cam NULL: rt_internal_pass_begin, else
-// rt_internal_frame_begin) and, exactly when the begin got as far as a stream,
+// rt_internal_frame_begin; with rt_scene_flags: rt_internal_scene_begin) and,
+// exactly when the begin got as far as a stream,
 // ends it with rt_internal_frame_end -- in end(), or on leaving the scope: a
 // pass that fails after enqueuing some of its work still has ev_done recorded
 // behind that work, so that the context's next pass on another stream, and
@@ -121,6 +149,10 @@ struct rt_pass_scope {
   rt_pass_scope(rt_context *c, const rt_camera *cam, const rt_params *prm, void *stream) : c_(c) {
     std::memset(&fs, 0, sizeof fs);
     status = cam ? rt_internal_frame_begin(c, cam, prm, stream, &fs) : rt_internal_pass_begin(c, stream, &fs);
+  }
+  rt_pass_scope(rt_context *c, rt_scene_flags sf, void *stream) : c_(c) {
+    std::memset(&fs, 0, sizeof fs);
+    status = rt_internal_scene_begin(c, sf.flags, stream, &fs);
   }
   rt_pass_scope(const rt_pass_scope &) = delete;
   ~rt_pass_scope() { (void)end(RT_OK); }
@@ -180,15 +212,15 @@ struct rt_sync_part {
 // also after a failure: the copies and launches read it and the host arrays.
 // wait() runs after a successful enqueue, before that drain: rt_aov waits
 // launch by launch there.
-template <size_t N, class Enqueue, class Wait = int (*)()>
-int rt_sync_pass(rt_context *c, const rt_camera *cam, const rt_params *prm, const rt_sync_part (&parts)[N],
-                 double *kernel_ms, Enqueue enqueue, Wait wait = [] { return (int)RT_OK; }) {
+// rt_sync_pass_in: the same in a scope the caller began on the context's own
+// stream (rt_trace's, which has no camera).
+template <size_t N, class Enqueue, class Wait>
+int rt_sync_pass_in(rt_pass_scope &ps, const rt_sync_part (&parts)[N], double *kernel_ms, Enqueue enqueue, Wait wait) {
   if (kernel_ms) *kernel_ms = 0.0;
   size_t off[N], total = 0;
   for (size_t k = 0; k < N; ++k) off[k] = total, total += (parts[k].bytes + 255) / 256 * 256;
   rt_device_buf<char> stage;  // (freed on leaving, after the drain)
   void *dev[N] = {};
-  rt_pass_scope ps(c, cam, prm, nullptr);  // (sets the device)
   const rt_frame_setup &fs = ps.fs;
   const auto run = [&]() -> int {
     if (ps.status != RT_OK) return ps.status;
@@ -216,6 +248,12 @@ int rt_sync_pass(rt_context *c, const rt_camera *cam, const rt_params *prm, cons
     if (dev[k] && parts[k].down) RT_HIP(hipMemcpy(parts[k].down, dev[k], parts[k].bytes, hipMemcpyDeviceToHost));
   if (kernel_ms) *kernel_ms = ms;
   return RT_OK;
+}
+template <size_t N, class Enqueue, class Wait = int (*)()>
+int rt_sync_pass(rt_context *c, const rt_camera *cam, const rt_params *prm, const rt_sync_part (&parts)[N],
+                 double *kernel_ms, Enqueue enqueue, Wait wait = [] { return (int)RT_OK; }) {
+  rt_pass_scope ps(c, cam, prm, nullptr);  // (sets the device)
+  return rt_sync_pass_in(ps, parts, kernel_ms, enqueue, wait);
 }
 
 #endif  // RTOW_RT_FRAME_H

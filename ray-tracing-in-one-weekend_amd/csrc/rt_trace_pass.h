@@ -1,7 +1,9 @@
 // rt_trace_pass.h -- internal: what the passes that trace the render's rays
 // into feature buffers share (the first-hit pass in rt_aov.hip, the
 // chain-following ones in rt_guides.hip and rt_route.hip, those two through
-// rt_chain.h as well; each includes this once, nothing else does).  On the device: the block's LDS copy of the layer grid, the tile ->
+// rt_chain.h as well; each includes this once, nothing else does) -- and
+// rt_trace.hip, which traces the caller's rays with the same walks, hit block,
+// launch table and synchronous form.  On the device: the block's LDS copy of the layer grid, the tile ->
 // pixel mapping, the run-time choice of closest_hit<>'s fold class, the hit
 // block up to the spurious-root test and from it to the shading normal, and
 // the six sums both passes write.  On the host: the launch table over a
@@ -207,15 +209,20 @@ constexpr auto launch_table(std::integer_sequence<int, V...>) {
   using fn = void (*)(unsigned, size_t, hipStream_t, const Params &);
   return std::array<fn, sizeof...(V)>{&launch_variant<K, Params, V>...};
 }
-// one launch over the frame's blocks, of the variant for these flags and this frame's grid
+// one launch over `blocks` blocks, of the variant for these flags and the setup's grid
 template <template <bool, bool, bool, int> class K, class Params>
-void launch_frame(const rt_frame_setup &fs, const rt_params *prm, const Params &a) {
+void launch_blocks(const rt_frame_setup &fs, uint32_t flags, unsigned blocks, const Params &a) {
   static constexpr auto table = launch_table<K, Params>(std::make_integer_sequence<int, 10>{});
   static_assert(rtk::kGridGlobal == 0 && rtk::kGridLds == 1 && rtk::kGridCells == 2, "variant = 2 + placement");
-  const bool bvh = (prm->flags & RT_FLAG_ACCEL_BVH) != 0;
+  const bool bvh = (flags & RT_FLAG_ACCEL_BVH) != 0;
   const int walk = !bvh ? 0 : (fs.grid ? 2 + fs.placement : 1);
-  const int v = ((prm->flags & RT_FLAG_OPEN_INTERVAL) ? 1 : 0) | (walk << 1);
-  table[(size_t)v]((unsigned)rt_frame_blocks(prm), fs.lds_bytes, fs.stream, a);
+  const int v = ((flags & RT_FLAG_OPEN_INTERVAL) ? 1 : 0) | (walk << 1);
+  table[(size_t)v](blocks, fs.lds_bytes, fs.stream, a);
+}
+// ... over the frame's blocks
+template <template <bool, bool, bool, int> class K, class Params>
+void launch_frame(const rt_frame_setup &fs, const rt_params *prm, const Params &a) {
+  launch_blocks<K>(fs, prm->flags, (unsigned)rt_frame_blocks(prm), a);
 }
 
 // This code object's copy of the lens sample's table, once per device.
@@ -225,7 +232,8 @@ void launch_frame(const rt_frame_setup &fs, const rt_params *prm, const Params &
 // the dynamic linker merges across librtow_aov.so and librtow_guides.so
 // whether or not they are linked -Bsymbolic: the library called second would
 // skip its upload and trace lens samples from a table of zeros.
-static hipError_t ensure_turn_table() {
+// (rt_trace.hip draws no lens sample and never calls it.)
+[[maybe_unused]] static hipError_t ensure_turn_table() {
   static std::mutex mu;
   static std::vector<char> done;
   int dev = 0;
@@ -242,6 +250,19 @@ static hipError_t ensure_turn_table() {
   return hipSuccess;
 }
 
+// After each launch of a pass on fs.stream: its status, and for the
+// synchronous caller an event to wait on.
+inline int trace_launched(const rt_frame_setup &fs, std::vector<hipEvent_t> *events) {
+  RT_HIP(hipGetLastError());  // a launch that cannot start stops the pass here
+  if (events) {
+    hipEvent_t ev = nullptr;
+    RT_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    events->push_back(ev);
+    RT_HIP(hipEventRecord(ev, fs.stream));
+  }
+  return RT_OK;
+}
+
 // The launches of one pass on fs.stream: launch(s_lo, s_cnt) for each of the
 // frame's sample ranges (rt_frame.h).  events (may be null): one event is
 // appended after each launch, for the synchronous caller to wait on in turn.
@@ -252,14 +273,7 @@ int trace_launches(const rt_frame_setup &fs, const rt_params *prm, std::vector<h
   return rt_sample_ranges(prm->spp, rt_samples_per_launch(prm->spp, frame_px, fs.launch_samples),
                           [&](int s_lo, int s_cnt) -> int {
                             launch(s_lo, s_cnt);
-                            RT_HIP(hipGetLastError());  // a launch that cannot start stops the pass here
-                            if (events) {
-                              hipEvent_t ev = nullptr;
-                              RT_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                              events->push_back(ev);
-                              RT_HIP(hipEventRecord(ev, fs.stream));
-                            }
-                            return RT_OK;
+                            return trace_launched(fs, events);
                           });
 }
 
@@ -267,13 +281,13 @@ int trace_launches(const rt_frame_setup &fs, const rt_params *prm, std::vector<h
 // rt_sync_pass): enqueue(fs, prm, dev, events) makes the launches into the
 // parts' device addresses dev[0 .. N), and the pass is waited for launch by
 // launch.
+// trace_sync_in: in a scope the caller began (rt_trace's, without a camera),
+// enqueue(fs, dev, events).
 template <size_t N, class Enqueue>
-int trace_sync(rt_context *c, const rt_camera *cam, const rt_params *prm, const rt_sync_part (&parts)[N],
-               Enqueue enqueue, double *kernel_ms) {
+int trace_sync_in(rt_pass_scope &ps, const rt_sync_part (&parts)[N], Enqueue enqueue, double *kernel_ms) {
   std::vector<hipEvent_t> events;
-  const int r = rt_sync_pass(
-      c, cam, prm, parts, kernel_ms,
-      [&](void *const *dev, const rt_frame_setup &fs) { return enqueue(fs, prm, dev, &events); },
+  const int r = rt_sync_pass_in(
+      ps, parts, kernel_ms, [&](void *const *dev, const rt_frame_setup &fs) { return enqueue(fs, dev, &events); },
       [&]() -> int {
         // wait launch by launch: a fault surfaces after the launch it happened in
         for (hipEvent_t ev : events) RT_HIP(hipEventSynchronize(ev));
@@ -281,6 +295,16 @@ int trace_sync(rt_context *c, const rt_camera *cam, const rt_params *prm, const 
       });
   for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
   return r;
+}
+template <size_t N, class Enqueue>
+int trace_sync(rt_context *c, const rt_camera *cam, const rt_params *prm, const rt_sync_part (&parts)[N],
+               Enqueue enqueue, double *kernel_ms) {
+  rt_pass_scope ps(c, cam, prm, nullptr);
+  return trace_sync_in(ps, parts,
+                       [&](const rt_frame_setup &fs, void *const *dev, std::vector<hipEvent_t> *events) {
+                         return enqueue(fs, prm, dev, events);
+                       },
+                       kernel_ms);
 }
 
 // One pass over N buffers (NULL = not wanted; none wanted: nothing to do), of

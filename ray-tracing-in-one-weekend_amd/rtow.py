@@ -37,9 +37,12 @@ UPSCALE_LIB_PATH = os.path.join(HERE, "librtow_upscale.so")
 GUIDES_LIB_PATH = os.path.join(HERE, "librtow_guides.so")
 # guide buffers of each pixel's dominant specular route (include/rt_route.h): an eighth
 ROUTE_LIB_PATH = os.path.join(HERE, "librtow_route.so")
+# closest-hit queries for caller-supplied ray batches (include/rt_trace.h): a ninth
+TRACE_LIB_PATH = os.path.join(HERE, "librtow_trace.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
+RT_ERR_NO_SCENE = -6
 RT_CAMERA_CPU, RT_CAMERA_GPU = 0, 1
 RT_FLAG_OPEN_INTERVAL = 1
 RT_FLAG_METAL_UNIT_VECTOR = 2
@@ -89,6 +92,11 @@ ROUTE_VERSION = 1  # include/rt_route.h RT_ROUTE_VERSION
 ROUTE_FIELDS = AOV_FIELDS + (("route", np.uint32, 1), ("matched", np.uint32, 1))
 ROUTE_STATE_BYTES_PER_PIXEL = 64  # RT_ROUTE_STATE_BYTES_PER_PIXEL: four planes of 16-byte entries
 ROUTE_NO_HIT = 0xFFFFFFFF  # "route" of a pixel without a hit sample
+TRACE_VERSION = 1  # include/rt_trace.h RT_TRACE_VERSION
+# rt_trace_hits' fields in order: (name, numpy dtype, channels); the ids of a ray without a hit
+TRACE_FIELDS = (("id", np.int32, 1), ("t", np.float32, 1), ("position", np.float32, 3), ("normal", np.float32, 3))
+TRACE_MISS, TRACE_INVALID = -1, -2  # RT_TRACE_MISS, RT_TRACE_INVALID
+TRACE_MAX_RAYS = 2 ** 31 - 1
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
 RT_OPT_BVH_COLLAPSE, RT_OPT_BVH_SIDE, RT_OPT_LAUNCH_SAMPLES, RT_OPT_GRID_FIT = 4, 5, 6, 7
@@ -164,6 +172,16 @@ class RouteOptions(ctypes.Structure):
     _fields_ = [("max_bounces", ctypes.c_int32), ("max_fuzz", ctypes.c_float), ("reserved", ctypes.c_uint32)]
 
 
+class TraceRays(ctypes.Structure):
+    """rt_trace_rays: n rays, origin and direction as device (rt_trace_async) or host (rt_trace) pointers."""
+    _fields_ = [("n", ctypes.c_uint64), ("origin", ctypes.c_void_p), ("direction", ctypes.c_void_p)]
+
+
+class TraceHits(ctypes.Structure):
+    """rt_trace_hits: device (rt_trace_async) or host (rt_trace) pointers, NULL = not wanted."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in TRACE_FIELDS]
+
+
 class DenoiseDesc(ctypes.Structure):
     """rt_denoise_desc: the frame, the options (0 = default) and device
     (rt_denoise_async) or host (rt_denoise) pointers."""
@@ -222,6 +240,7 @@ _resolve_lib = None
 _upscale_lib = None
 _guides_lib = None
 _route_lib = None
+_trace_lib = None
 
 
 def _missing(path):
@@ -488,6 +507,19 @@ def aov_lib():
             "rt_aov": (None, [ctypes.c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Params),
                               ctypes.POINTER(AovBuffers), ctypes.POINTER(ctypes.c_double)])})
     return _aov_lib
+
+
+def trace_lib():
+    """Load librtow_trace.so, closest-hit queries for ray batches (raises if it
+    has not been built)."""
+    global _trace_lib
+    if _trace_lib is None:
+        _trace_lib = _load_pass(TRACE_LIB_PATH, "rt_trace_version", TRACE_VERSION, {
+            "rt_trace_async": (None, [ctypes.c_void_p, ctypes.POINTER(TraceRays), ctypes.POINTER(TraceHits),
+                                      ctypes.c_uint32, ctypes.c_void_p]),
+            "rt_trace": (None, [ctypes.c_void_p, ctypes.POINTER(TraceRays), ctypes.POINTER(TraceHits),
+                                ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)])})
+    return _trace_lib
 
 
 def lib():
@@ -860,6 +892,51 @@ class Context:
         device pointers; names left out are not computed."""
         self._feature_pass_async(AOV_FIELDS, AovBuffers, aov_lib().rt_aov_async, "rt_aov_async", cam, params,
                                  dev_ptrs, stream)
+
+    def trace(self, origins, directions, which=("id", "t", "position", "normal"), flags=0):
+        """Closest hits of a batch of rays (rt_trace, include/rt_trace.h),
+        synchronously: origins and directions are (n, 3) arrays (converted to
+        contiguous float32; directions unnormalised), the result a dict of
+        numpy arrays for the names in `which` -- "id" int32 (n,) (TRACE_MISS,
+        TRACE_INVALID), "t" float32 (n,) (+inf without a hit), "position" and
+        "normal" float32 (n, 3) -- plus "kernel_ms".  flags: the interval and
+        acceleration flags of a render."""
+        _reject_unknown(which, [f[0] for f in TRACE_FIELDS], "trace outputs")
+        o = np.ascontiguousarray(origins, np.float32)
+        d = np.ascontiguousarray(directions, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError(f"origins and directions must both be (n, 3), got {o.shape} and {d.shape}")
+        n = o.shape[0]
+        rays = TraceRays(n=n, origin=o.ctypes.data, direction=d.ctypes.data)
+        out, hits = {}, TraceHits()
+        for field, dt, ch in TRACE_FIELDS:
+            if field in which:
+                out[field] = np.zeros((n, 3) if ch == 3 else (n,), dt)
+                setattr(hits, field, out[field].ctypes.data)
+        ms = ctypes.c_double()
+        check(trace_lib().rt_trace(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags), ctypes.byref(ms)),
+              "rt_trace")
+        out["kernel_ms"] = ms.value
+        return out
+
+    def trace_async(self, dev_ptrs, n, flags=0, stream=0):
+        """Enqueue the batch query (rt_trace_async) on raw device pointers
+        (e.g. torch tensor.data_ptr() of contiguous float32 (n, 3) / int32 (n,)
+        tensors): dev_ptrs maps "origin", "direction" and the wanted names of
+        TRACE_FIELDS to device pointers; outputs left out are not computed."""
+        _reject_unknown(dev_ptrs, ["origin", "direction"] + [f[0] for f in TRACE_FIELDS], "trace buffers")
+        missing = [k for k in ("origin", "direction") if k not in dev_ptrs]
+        if missing:
+            raise ValueError(f"trace_async: {missing} missing")
+        if not 0 <= int(n) <= TRACE_MAX_RAYS:
+            raise ValueError(f"trace_async: n = {n} is outside 0 .. {TRACE_MAX_RAYS}")
+        rays = TraceRays(n=int(n), origin=dev_ptrs["origin"], direction=dev_ptrs["direction"])
+        hits = TraceHits()
+        for field, _, _ in TRACE_FIELDS:
+            if field in dev_ptrs:
+                setattr(hits, field, dev_ptrs[field])
+        check(trace_lib().rt_trace_async(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags),
+                                         ctypes.c_void_p(stream)), "rt_trace_async")
 
     def guides(self, cam, params, which=tuple(f[0] for f in GUIDES_FIELDS), max_bounces=None, max_fuzz=None):
         """Feature buffers that follow each sample's path through mirrors and
