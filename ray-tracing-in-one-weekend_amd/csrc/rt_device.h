@@ -794,9 +794,12 @@ __device__ __forceinline__ void grid_walk(float ox, float oz, float ix, float iz
 // (kernargs()): they live in SGPRs for the walk only, not across the whole
 // bounce loop (SGPR pressure).
 // FOLD: the grid build's form of the first extras group (scan_extras).
+// seed: the state the walk starts from.  rt_segment.hip alone passes one,
+// (limit, 0): only roots strictly below the limit are candidates, and every
+// walk stops at it as at a hit's tmax.
 template <bool OPEN, bool BVH, bool STATS, bool GRID, int GP, int FOLD>
 __device__ __forceinline__ hit_state closest_hit(float ox, float oy, float oz, float dx, float dy, float dz,
-                                                 float tmin, work_ctr &wc) {
+                                                 float tmin, work_ctr &wc, const hit_state seed = no_hit()) {
   const kparams p = kernargs();
   const RT_CONST pair_geom *__restrict__ scan_geom = as_const(p.scan_geom);
   const RT_CONST pair_geom *__restrict__ geom = as_const(p.geom);
@@ -807,7 +810,7 @@ __device__ __forceinline__ hit_state closest_hit(float ox, float oy, float oz, f
   const float nk1 = -dot3(ox, oy, oz, dx, dy, dz);
   const float o2 = dot3(ox, oy, oz, ox, oy, oz);
   const float ox2 = -2.0f * ox, oy2 = -2.0f * oy, oz2 = -2.0f * oz;
-  hit_state hs = no_hit();
+  hit_state hs = seed;
   // the per-ray terms, splatted into pairs for the packed scans (the grid
   // build's extras and walk read the .x halves only)
   auto splat = [&]() {

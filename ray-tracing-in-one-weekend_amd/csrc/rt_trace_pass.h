@@ -94,18 +94,19 @@ __device__ __forceinline__ bool trace_pixel_of(const kparams &p, trace_pixel &px
 
 // closest_hit<> in the render's choice of the first extras group's form
 // (kparams extras_fold), taken here at run time: one kernel per walk, the
-// class a wave-uniform branch
+// class a wave-uniform branch.  seed: closest_hit<>'s (rt_segment.hip's limit).
 template <bool OPEN, bool BVH, bool GRID, int GP>
 __device__ __forceinline__ hit_state walk(const kparams &p, float ox, float oy, float oz, float dx, float dy, float dz,
-                                          float tmin, work_ctr &wc) {
+                                          float tmin, work_ctr &wc, const hit_state seed = no_hit()) {
   const int fold = GRID ? p.extras_fold : 0;
   if (fold == (kFoldLead | kFoldRest))
-    return closest_hit<OPEN, BVH, false, GRID, GP, GRID ? kFoldLead | kFoldRest : 0>(ox, oy, oz, dx, dy, dz, tmin, wc);
+    return closest_hit<OPEN, BVH, false, GRID, GP, GRID ? kFoldLead | kFoldRest : 0>(ox, oy, oz, dx, dy, dz, tmin, wc,
+                                                                                     seed);
   if (fold == kFoldLead)
-    return closest_hit<OPEN, BVH, false, GRID, GP, GRID ? kFoldLead : 0>(ox, oy, oz, dx, dy, dz, tmin, wc);
+    return closest_hit<OPEN, BVH, false, GRID, GP, GRID ? kFoldLead : 0>(ox, oy, oz, dx, dy, dz, tmin, wc, seed);
   if (fold == kFoldRest)
-    return closest_hit<OPEN, BVH, false, GRID, GP, GRID ? kFoldRest : 0>(ox, oy, oz, dx, dy, dz, tmin, wc);
-  return closest_hit<OPEN, BVH, false, GRID, GP, 0>(ox, oy, oz, dx, dy, dz, tmin, wc);
+    return closest_hit<OPEN, BVH, false, GRID, GP, GRID ? kFoldRest : 0>(ox, oy, oz, dx, dy, dz, tmin, wc, seed);
+  return closest_hit<OPEN, BVH, false, GRID, GP, 0>(ox, oy, oz, dx, dy, dz, tmin, wc, seed);
 }
 
 // render_kernel's hit block in two steps, with the caller's spurious-root test

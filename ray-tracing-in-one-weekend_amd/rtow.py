@@ -39,6 +39,8 @@ GUIDES_LIB_PATH = os.path.join(HERE, "librtow_guides.so")
 ROUTE_LIB_PATH = os.path.join(HERE, "librtow_route.so")
 # closest-hit queries for caller-supplied ray batches (include/rt_trace.h): a ninth
 TRACE_LIB_PATH = os.path.join(HERE, "librtow_trace.so")
+# the same queries within a per-ray distance limit (include/rt_segment.h): a tenth
+SEGMENT_LIB_PATH = os.path.join(HERE, "librtow_segment.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
@@ -97,6 +99,10 @@ TRACE_VERSION = 1  # include/rt_trace.h RT_TRACE_VERSION
 TRACE_FIELDS = (("id", np.int32, 1), ("t", np.float32, 1), ("position", np.float32, 3), ("normal", np.float32, 3))
 TRACE_MISS, TRACE_INVALID = -1, -2  # RT_TRACE_MISS, RT_TRACE_INVALID
 TRACE_MAX_RAYS = 2 ** 31 - 1
+SEGMENT_VERSION = 1  # include/rt_segment.h RT_SEGMENT_VERSION
+# rt_segment_hits' fields in order: "blocked" (uint8), then rt_trace_hits'; the ids are rt_trace's
+SEGMENT_FIELDS = (("blocked", np.uint8, 1),) + TRACE_FIELDS
+SEGMENT_MISS, SEGMENT_INVALID = -1, -2  # RT_SEGMENT_MISS, RT_SEGMENT_INVALID
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
 RT_OPT_BVH_COLLAPSE, RT_OPT_BVH_SIDE, RT_OPT_LAUNCH_SAMPLES, RT_OPT_GRID_FIT = 4, 5, 6, 7
@@ -182,6 +188,16 @@ class TraceHits(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name, _, _ in TRACE_FIELDS]
 
 
+class SegmentRays(ctypes.Structure):
+    """rt_segment_rays: rt_trace_rays and t_max, n floats in units of the direction (NULL = +inf for every ray)."""
+    _fields_ = TraceRays._fields_ + [("t_max", ctypes.c_void_p)]
+
+
+class SegmentHits(ctypes.Structure):
+    """rt_segment_hits: device (rt_segment_async) or host (rt_segment) pointers, NULL = not wanted."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in SEGMENT_FIELDS]
+
+
 class DenoiseDesc(ctypes.Structure):
     """rt_denoise_desc: the frame, the options (0 = default) and device
     (rt_denoise_async) or host (rt_denoise) pointers."""
@@ -241,6 +257,7 @@ _upscale_lib = None
 _guides_lib = None
 _route_lib = None
 _trace_lib = None
+_segment_lib = None
 
 
 def _missing(path):
@@ -520,6 +537,18 @@ def trace_lib():
             "rt_trace": (None, [ctypes.c_void_p, ctypes.POINTER(TraceRays), ctypes.POINTER(TraceHits),
                                 ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)])})
     return _trace_lib
+
+
+def segment_lib():
+    """Load librtow_segment.so, closest hits within a per-ray distance limit
+    (raises if it has not been built)."""
+    global _segment_lib
+    if _segment_lib is None:
+        head = [ctypes.c_void_p, ctypes.POINTER(SegmentRays), ctypes.POINTER(SegmentHits), ctypes.c_uint32]
+        _segment_lib = _load_pass(SEGMENT_LIB_PATH, "rt_segment_version", SEGMENT_VERSION, {
+            "rt_segment_async": (None, head + [ctypes.c_void_p]),
+            "rt_segment": (None, head + [ctypes.POINTER(ctypes.c_double)])})
+    return _segment_lib
 
 
 def lib():
@@ -937,6 +966,94 @@ class Context:
                 setattr(hits, field, dev_ptrs[field])
         check(trace_lib().rt_trace_async(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags),
                                          ctypes.c_void_p(stream)), "rt_trace_async")
+
+    def segment(self, origins, directions, t_max=None, which=tuple(f[0] for f in SEGMENT_FIELDS), flags=0):
+        """Closest hits of a batch of rays within a distance limit per ray
+        (rt_segment, include/rt_segment.h), synchronously.  origins and
+        directions as in trace(); t_max an (n,) array in units of the
+        unnormalised direction (t_max = 1: the segment from o to o + d), a
+        scalar for every ray, or None for no limit.  A candidate counts only
+        strictly below the limit.  The result: trace()'s dict plus "blocked",
+        uint8 (n,), 1 with a hit on the segment (SEGMENT_MISS: nothing on it;
+        SEGMENT_INVALID: trace()'s invalid forms, or a NaN t_max)."""
+        _reject_unknown(which, [f[0] for f in SEGMENT_FIELDS], "segment outputs")
+        o = np.ascontiguousarray(origins, np.float32)
+        d = np.ascontiguousarray(directions, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError(f"origins and directions must both be (n, 3), got {o.shape} and {d.shape}")
+        n = o.shape[0]
+        tm = None
+        if t_max is not None:
+            tm = np.asarray(t_max, np.float32)
+            if tm.ndim not in (0, 1) or (tm.ndim == 1 and tm.shape[0] != n):
+                raise ValueError(f"t_max must be a scalar or ({n},), got {tm.shape}")
+            tm = np.ascontiguousarray(np.broadcast_to(tm, (n,)))
+        rays = SegmentRays(n=n, origin=o.ctypes.data, direction=d.ctypes.data,
+                           t_max=tm.ctypes.data if tm is not None and n else None)
+        out, hits = {}, SegmentHits()
+        for field, dt, ch in SEGMENT_FIELDS:
+            if field in which:
+                out[field] = np.zeros((n, 3) if ch == 3 else (n,), dt)
+                setattr(hits, field, out[field].ctypes.data)
+        ms = ctypes.c_double()
+        check(segment_lib().rt_segment(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags), ctypes.byref(ms)),
+              "rt_segment")
+        out["kernel_ms"] = ms.value
+        return out
+
+    def segment_async(self, dev_ptrs, n, flags=0, stream=0):
+        """Enqueue the limited query (rt_segment_async) on raw device pointers
+        (e.g. torch tensor.data_ptr() of contiguous float32 (n, 3) / (n,),
+        int32 (n,) and uint8 (n,) tensors): dev_ptrs maps "origin",
+        "direction", optionally "t_max" (left out: no limit) and the wanted
+        names of SEGMENT_FIELDS to device pointers; outputs left out are not
+        computed."""
+        _reject_unknown(dev_ptrs, ["origin", "direction", "t_max"] + [f[0] for f in SEGMENT_FIELDS], "segment buffers")
+        missing = [k for k in ("origin", "direction") if k not in dev_ptrs]
+        if missing:
+            raise ValueError(f"segment_async: {missing} missing")
+        if not 0 <= int(n) <= TRACE_MAX_RAYS:
+            raise ValueError(f"segment_async: n = {n} is outside 0 .. {TRACE_MAX_RAYS}")
+        rays = SegmentRays(n=int(n), origin=dev_ptrs["origin"], direction=dev_ptrs["direction"],
+                           t_max=dev_ptrs.get("t_max"))
+        hits = SegmentHits()
+        for field, _, _ in SEGMENT_FIELDS:
+            if field in dev_ptrs:
+                setattr(hits, field, dev_ptrs[field])
+        check(segment_lib().rt_segment_async(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags),
+                                             ctypes.c_void_p(stream)), "rt_segment_async")
+
+    def visible(self, a, b, shrink=1e-3, flags=0):
+        """Whether point b[i] is visible from point a[i]: a bool (n,) array,
+        True where no sphere lies on the segment.  a and b are (n, 3) (or one
+        of them a single point, (3,)); the query is segment() with d = b - a
+        and t_max = 1 - shrink, and the answer is not blocked.
+
+        Both ends are open, each by a fraction of the segment's length.  At a,
+        t_min = 0.001 in units of d skips everything within 0.001 |b - a| of
+        the start, so a segment that starts ON a surface (a shading point, a
+        trace() position) does not see that surface -- and would not see
+        another one that close either.  At b, shrink cuts the last shrink
+        |b - a| off: with the default a segment that ends ON a surface (a point
+        on a light, another hit point) stops 0.001 |b - a| short of it and is
+        not blocked by it, where shrink = 0 leaves that to the last bit of the
+        surface's root.  A point deeper inside a sphere than those margins is
+        hidden by the sphere's shell.  The answer is ~blocked and nothing else:
+        a[i] == b[i] (a zero direction, an invalid ray) reads as visible, a
+        point from itself, and so does a pair with a non-finite component; use
+        segment() and its "id" to tell those apart.  shrink = 1 leaves nothing
+        of the segment, and every pair reads as visible."""
+        a = np.asarray(a, np.float32)
+        b = np.asarray(b, np.float32)
+        if a.ndim not in (1, 2) or b.ndim not in (1, 2) or a.shape[-1] != 3 or b.shape[-1] != 3:
+            raise ValueError(f"a and b must be (n, 3) or (3,), got {a.shape} and {b.shape}")
+        if a.ndim == 2 and b.ndim == 2 and a.shape != b.shape:
+            raise ValueError(f"a and b must hold the same number of points, got {a.shape} and {b.shape}")
+        if not 0.0 <= float(shrink) <= 1.0:  # (a NaN fails too)
+            raise ValueError(f"shrink = {shrink} is outside 0 .. 1")
+        a, b = np.broadcast_arrays(np.atleast_2d(a), np.atleast_2d(b))
+        got = self.segment(a, b - a, np.float32(1.0) - np.float32(shrink), which=("blocked",), flags=flags)
+        return got["blocked"] == 0
 
     def guides(self, cam, params, which=tuple(f[0] for f in GUIDES_FIELDS), max_bounces=None, max_fuzz=None):
         """Feature buffers that follow each sample's path through mirrors and
