@@ -2,8 +2,9 @@
 // into feature buffers share (the first-hit pass in rt_aov.hip, the
 // chain-following ones in rt_guides.hip and rt_route.hip, those two through
 // rt_chain.h as well; each includes this once, nothing else does) -- and
-// rt_trace.hip, which traces the caller's rays with the same walks, hit block,
-// launch table and synchronous form.  On the device: the block's LDS copy of the layer grid, the tile ->
+// rt_trace.hip and rt_segment.hip (through rt_ray_batch.h), which trace the
+// caller's rays with the same walks, hit block, launch table and synchronous
+// form.  On the device: the block's LDS copy of the layer grid, the tile ->
 // pixel mapping, the run-time choice of closest_hit<>'s fold class, the hit
 // block up to the spurious-root test and from it to the shading normal, and
 // the six sums both passes write.  On the host: the launch table over a

@@ -551,6 +551,11 @@ def segment_lib():
     return _segment_lib
 
 
+# the two ray-batch queries, rt_<kind> and rt_<kind>_async: output fields, structures, library
+_RAY_BATCH = {"trace": (TRACE_FIELDS, TraceRays, TraceHits, trace_lib),
+              "segment": (SEGMENT_FIELDS, SegmentRays, SegmentHits, segment_lib)}
+
+
 def lib():
     """Load librtow.so (raises if it has not been built)."""
     global _lib
@@ -922,6 +927,51 @@ class Context:
         self._feature_pass_async(AOV_FIELDS, AovBuffers, aov_lib().rt_aov_async, "rt_aov_async", cam, params,
                                  dev_ptrs, stream)
 
+    def _ray_batch(self, kind, origins, directions, t_max, which, flags):
+        """Context.trace / Context.segment: the arrays, the outputs in `which`, the call."""
+        fields, rays_type, hits_type, lib = _RAY_BATCH[kind]
+        _reject_unknown(which, [f[0] for f in fields], f"{kind} outputs")
+        o = np.ascontiguousarray(origins, np.float32)
+        d = np.ascontiguousarray(directions, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError(f"origins and directions must both be (n, 3), got {o.shape} and {d.shape}")
+        n = o.shape[0]
+        rays = rays_type(n=n, origin=o.ctypes.data, direction=d.ctypes.data)
+        if t_max is not None:
+            tm = np.asarray(t_max, np.float32)
+            if tm.ndim not in (0, 1) or (tm.ndim == 1 and tm.shape[0] != n):
+                raise ValueError(f"t_max must be a scalar or ({n},), got {tm.shape}")
+            tm = np.ascontiguousarray(np.broadcast_to(tm, (n,)))
+            rays.t_max = tm.ctypes.data if n else None
+        out, hits = {}, hits_type()
+        for field, dt, ch in fields:
+            if field in which:
+                out[field] = np.zeros((n, 3) if ch == 3 else (n,), dt)
+                setattr(hits, field, out[field].ctypes.data)
+        ms = ctypes.c_double()
+        check(getattr(lib(), f"rt_{kind}")(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags),
+                                            ctypes.byref(ms)), f"rt_{kind}")
+        out["kernel_ms"] = ms.value
+        return out
+
+    def _ray_batch_async(self, kind, dev_ptrs, n, flags, stream):
+        """Context.trace_async / Context.segment_async: the names, the range of n, the device pointers, the call."""
+        fields, rays_type, hits_type, lib = _RAY_BATCH[kind]
+        inputs, outputs = [f[0] for f in rays_type._fields_[1:]], [f[0] for f in fields]
+        _reject_unknown(dev_ptrs, inputs + outputs, f"{kind} buffers")
+        missing = [k for k in ("origin", "direction") if k not in dev_ptrs]
+        if missing:
+            raise ValueError(f"{kind}_async: {missing} missing")
+        if not 0 <= int(n) <= TRACE_MAX_RAYS:
+            raise ValueError(f"{kind}_async: n = {n} is outside 0 .. {TRACE_MAX_RAYS}")
+        rays, hits = rays_type(n=int(n)), hits_type()
+        for struct, names in ((rays, inputs), (hits, outputs)):
+            for field in names:
+                if field in dev_ptrs:
+                    setattr(struct, field, dev_ptrs[field])
+        check(getattr(lib(), f"rt_{kind}_async")(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags),
+                                                  ctypes.c_void_p(stream)), f"rt_{kind}_async")
+
     def trace(self, origins, directions, which=("id", "t", "position", "normal"), flags=0):
         """Closest hits of a batch of rays (rt_trace, include/rt_trace.h),
         synchronously: origins and directions are (n, 3) arrays (converted to
@@ -930,42 +980,14 @@ class Context:
         TRACE_INVALID), "t" float32 (n,) (+inf without a hit), "position" and
         "normal" float32 (n, 3) -- plus "kernel_ms".  flags: the interval and
         acceleration flags of a render."""
-        _reject_unknown(which, [f[0] for f in TRACE_FIELDS], "trace outputs")
-        o = np.ascontiguousarray(origins, np.float32)
-        d = np.ascontiguousarray(directions, np.float32)
-        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
-            raise ValueError(f"origins and directions must both be (n, 3), got {o.shape} and {d.shape}")
-        n = o.shape[0]
-        rays = TraceRays(n=n, origin=o.ctypes.data, direction=d.ctypes.data)
-        out, hits = {}, TraceHits()
-        for field, dt, ch in TRACE_FIELDS:
-            if field in which:
-                out[field] = np.zeros((n, 3) if ch == 3 else (n,), dt)
-                setattr(hits, field, out[field].ctypes.data)
-        ms = ctypes.c_double()
-        check(trace_lib().rt_trace(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags), ctypes.byref(ms)),
-              "rt_trace")
-        out["kernel_ms"] = ms.value
-        return out
+        return self._ray_batch("trace", origins, directions, None, which, flags)
 
     def trace_async(self, dev_ptrs, n, flags=0, stream=0):
         """Enqueue the batch query (rt_trace_async) on raw device pointers
         (e.g. torch tensor.data_ptr() of contiguous float32 (n, 3) / int32 (n,)
         tensors): dev_ptrs maps "origin", "direction" and the wanted names of
         TRACE_FIELDS to device pointers; outputs left out are not computed."""
-        _reject_unknown(dev_ptrs, ["origin", "direction"] + [f[0] for f in TRACE_FIELDS], "trace buffers")
-        missing = [k for k in ("origin", "direction") if k not in dev_ptrs]
-        if missing:
-            raise ValueError(f"trace_async: {missing} missing")
-        if not 0 <= int(n) <= TRACE_MAX_RAYS:
-            raise ValueError(f"trace_async: n = {n} is outside 0 .. {TRACE_MAX_RAYS}")
-        rays = TraceRays(n=int(n), origin=dev_ptrs["origin"], direction=dev_ptrs["direction"])
-        hits = TraceHits()
-        for field, _, _ in TRACE_FIELDS:
-            if field in dev_ptrs:
-                setattr(hits, field, dev_ptrs[field])
-        check(trace_lib().rt_trace_async(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags),
-                                         ctypes.c_void_p(stream)), "rt_trace_async")
+        self._ray_batch_async("trace", dev_ptrs, n, flags, stream)
 
     def segment(self, origins, directions, t_max=None, which=tuple(f[0] for f in SEGMENT_FIELDS), flags=0):
         """Closest hits of a batch of rays within a distance limit per ray
@@ -976,30 +998,7 @@ class Context:
         strictly below the limit.  The result: trace()'s dict plus "blocked",
         uint8 (n,), 1 with a hit on the segment (SEGMENT_MISS: nothing on it;
         SEGMENT_INVALID: trace()'s invalid forms, or a NaN t_max)."""
-        _reject_unknown(which, [f[0] for f in SEGMENT_FIELDS], "segment outputs")
-        o = np.ascontiguousarray(origins, np.float32)
-        d = np.ascontiguousarray(directions, np.float32)
-        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
-            raise ValueError(f"origins and directions must both be (n, 3), got {o.shape} and {d.shape}")
-        n = o.shape[0]
-        tm = None
-        if t_max is not None:
-            tm = np.asarray(t_max, np.float32)
-            if tm.ndim not in (0, 1) or (tm.ndim == 1 and tm.shape[0] != n):
-                raise ValueError(f"t_max must be a scalar or ({n},), got {tm.shape}")
-            tm = np.ascontiguousarray(np.broadcast_to(tm, (n,)))
-        rays = SegmentRays(n=n, origin=o.ctypes.data, direction=d.ctypes.data,
-                           t_max=tm.ctypes.data if tm is not None and n else None)
-        out, hits = {}, SegmentHits()
-        for field, dt, ch in SEGMENT_FIELDS:
-            if field in which:
-                out[field] = np.zeros((n, 3) if ch == 3 else (n,), dt)
-                setattr(hits, field, out[field].ctypes.data)
-        ms = ctypes.c_double()
-        check(segment_lib().rt_segment(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags), ctypes.byref(ms)),
-              "rt_segment")
-        out["kernel_ms"] = ms.value
-        return out
+        return self._ray_batch("segment", origins, directions, t_max, which, flags)
 
     def segment_async(self, dev_ptrs, n, flags=0, stream=0):
         """Enqueue the limited query (rt_segment_async) on raw device pointers
@@ -1008,20 +1007,7 @@ class Context:
         "direction", optionally "t_max" (left out: no limit) and the wanted
         names of SEGMENT_FIELDS to device pointers; outputs left out are not
         computed."""
-        _reject_unknown(dev_ptrs, ["origin", "direction", "t_max"] + [f[0] for f in SEGMENT_FIELDS], "segment buffers")
-        missing = [k for k in ("origin", "direction") if k not in dev_ptrs]
-        if missing:
-            raise ValueError(f"segment_async: {missing} missing")
-        if not 0 <= int(n) <= TRACE_MAX_RAYS:
-            raise ValueError(f"segment_async: n = {n} is outside 0 .. {TRACE_MAX_RAYS}")
-        rays = SegmentRays(n=int(n), origin=dev_ptrs["origin"], direction=dev_ptrs["direction"],
-                           t_max=dev_ptrs.get("t_max"))
-        hits = SegmentHits()
-        for field, _, _ in SEGMENT_FIELDS:
-            if field in dev_ptrs:
-                setattr(hits, field, dev_ptrs[field])
-        check(segment_lib().rt_segment_async(self._h, ctypes.byref(rays), ctypes.byref(hits), int(flags),
-                                             ctypes.c_void_p(stream)), "rt_segment_async")
+        self._ray_batch_async("segment", dev_ptrs, n, flags, stream)
 
     def visible(self, a, b, shrink=1e-3, flags=0):
         """Whether point b[i] is visible from point a[i]: a bool (n,) array,

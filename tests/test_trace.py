@@ -150,9 +150,12 @@ def test_trace_python_checks_names_and_shapes(rtow):
 
 
 # ---- device code --------------------------------------------------------------
-def test_trace_device_code_has_ten_variants_and_no_flat_or_scratch_instructions(rtow, tmp_path):
-    """test_aov.py's procedure on librtow_trace.so: the ten variants (open x
-    {scan, BVH, grid x 3 placements}), global_*, ds_* and scalar loads, no
+@pytest.mark.parametrize("lib_path, limit", [("TRACE_LIB_PATH", 0), ("SEGMENT_LIB_PATH", 1)], ids=["trace", "segment"])
+def test_trace_device_code_has_ten_variants_and_no_flat_or_scratch_instructions(rtow, tmp_path, lib_path, limit):
+    """test_aov.py's procedure on librtow_trace.so and librtow_segment.so: the
+    ten variants (open x {scan, BVH, grid x 3 placements}) of
+    csrc/rt_ray_batch.h's kernel, each library's without (LIMIT 0) or with
+    (1) the limit and none of the other's; global_*, ds_* and scalar loads, no
     flat_* and no scratch_* / buffer_* (spill) instruction."""
     import shutil
     llvm = "/opt/rocm/lib/llvm/bin"
@@ -160,13 +163,14 @@ def test_trace_device_code_has_ten_variants_and_no_flat_or_scratch_instructions(
         pytest.skip("llvm-objdump / objcopy not available")
     fat = tmp_path / "fatbin.bin"
     co = tmp_path / "gfx950.co"
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", rtow.TRACE_LIB_PATH, str(fat)],
+    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", getattr(rtow, lib_path), str(fat)],
                    check=True)
     subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + str(fat),
                     "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + str(co)], check=True)
     dis = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", "--no-show-raw-insn", str(co)],
                          check=True, capture_output=True, text=True).stdout
-    assert len(re.findall(r"^[0-9a-f]+ <_ZN3rtk12trace_kernel\w+>:$", dis, re.M)) == 10
+    kernels = re.findall(r"^[0-9a-f]+ <_ZN3rtk12batch_kernelILb([01])E\w+>:$", dis, re.M)
+    assert kernels == [str(limit)] * 10, kernels
     ops = re.findall(r"^\s+((?:flat|global|ds|scratch|buffer)_\w+)", dis, re.M)
     assert sum(o.startswith("global_") for o in ops) > 100 and sum(o.startswith("ds_") for o in ops) >= 8
     other = sorted(set(o for o in ops if not o.startswith(("global_", "ds_"))))

@@ -1,0 +1,197 @@
+"""Time the two ray-batch queries (include/rt_trace.h, include/rt_segment.h):
+final scene, layer grid, everything in device buffers, HIP events around
+repeated enqueues after a warm-up.  There is no target in either mode.
+
+  python tools/ray_batch_time.py --mode trace   [--width 3840 --height 2160 --reps 20 --log profiles/trace_pass.log]
+  python tools/ray_batch_time.py --mode segment [--width 3840 --height 2160 --reps 20 --log profiles/segment_pass.log]
+
+trace: rt_trace next to the first-hit pass (include/rt_aov.h) on the same rays,
+the pinhole camera's pixel-centre rays of the frame.  Batch (a) holds the rays
+in 8x8-tile order, a wave's 64 rays one tile of the frame as in rt_aov; batch
+(b) the same rays in a random permutation.  (a) is read against rt_aov at
+1 spp on the same frame in the same run (rt_aov jitters its rays inside the
+pixel and writes 52 bytes per pixel where rt_trace reads 24 and writes 32),
+and (b) shows what incoherent waves cost.
+
+segment: rt_segment next to rt_trace on secondary rays.  rt_trace on batch
+(a); from every hit one cosine-weighted hemisphere ray, origin = position,
+direction = normal + a uniform unit vector (numpy, seeded), kept in the
+primary rays' order.  These are the rays of an ambient-occlusion or a diffuse
+bounce pass: neighbours start close together and fan out.  rt_trace is timed
+on them twice, first and last; the spread of the two is the run's noise.
+rt_segment is timed without a limit (t_max = +inf: the same walks, one more
+input) and at world lengths 4, 1 and 0.25: the lines say what a limit saves on
+this scene.
+
+Prints the times and writes the same lines to --log."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "ray-tracing-in-one-weekend_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402  (before rtow: INTEGRATION.md, "Loading")
+
+import rtow  # noqa: E402
+
+LENGTHS = (4.0, 1.0, 0.25)
+FLAGS = rtow.RT_FLAG_ACCEL_BVH
+
+
+def timed(fn, reps, stream):
+    fn()
+    fn()
+    stream.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record(stream)
+    for _ in range(reps):
+        fn()
+    t1.record(stream)
+    t1.synchronize()
+    return t0.elapsed_time(t1) / reps
+
+
+def pixel_centre_rays(cam, w, h):
+    """The CPU-model pinhole camera's rays through the pixel centres, float32
+    (w * h, 3) origins and unnormalised directions (camera_dir with u = 0.5)."""
+    f32 = np.float32
+    col, row = np.meshgrid(np.arange(w, dtype=f32), np.arange(h, dtype=f32))
+    fs = (col + f32(0.5)) * f32(1.0 / (w - 1))
+    ft = (f32(h - 1) - row + f32(0.5)) * f32(1.0 / (h - 1))
+    eye, corner, hz, vt = (np.array(v[:], f32) for v in (cam.eye, cam.corner, cam.horiz, cam.vert))
+    d = corner + fs[..., None] * hz + ft[..., None] * vt - eye
+    return np.broadcast_to(eye, d.shape).reshape(-1, 3).copy(), d.astype(f32).reshape(-1, 3)
+
+
+def tile_order(w, h, tile=8):
+    """Pixel indices in 8x8-tile order (tiles row-major, pixels row-major in a tile)."""
+    idx = np.arange(w * h).reshape(h, w)
+    assert w % tile == 0 and h % tile == 0
+    return idx.reshape(h // tile, tile, w // tile, tile).transpose(0, 2, 1, 3).reshape(-1)
+
+
+def hemisphere_rays(position, normal, seed):
+    """One cosine-weighted direction per hit: normal + a uniform unit vector
+    (float32; a sum shorter than 1e-3 is replaced by the normal)."""
+    rng = np.random.default_rng(seed)
+    u = rng.normal(size=position.shape).astype(np.float32)
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    d = normal + u
+    short = np.linalg.norm(d, axis=1) < 1e-3
+    d[short] = normal[short]
+    return position, d.astype(np.float32)
+
+
+def device_batch(o, d, dev, fields):
+    """The rays on the device and zeroed outputs for `fields`: (tensors kept alive, name -> device pointer)."""
+    n = len(o)
+    t = {"origin": torch.from_numpy(np.ascontiguousarray(o)).to(dev),
+         "direction": torch.from_numpy(np.ascontiguousarray(d)).to(dev)}
+    for name, dt, ch in fields:
+        t[name] = torch.zeros((n, 3) if ch == 3 else (n,), dtype=getattr(torch, np.dtype(dt).name), device=dev)
+    torch.cuda.synchronize()
+    return t, {k: v.data_ptr() for k, v in t.items()}
+
+
+def trace_mode(ctx, cam, w, h, reps, dev, stream, say):
+    n, s = w * h, stream.cuda_stream
+    o, d = pixel_centre_rays(cam, w, h)
+    order = {"(a) 8x8-tile order": tile_order(w, h), "(b) random permutation": np.random.default_rng(1).permutation(n)}
+    aov = {}
+    for name, _, ch in rtow.AOV_FIELDS:
+        dt = torch.float32 if name in ("depth", "position", "normal", "albedo") else torch.int32
+        aov[name] = torch.zeros((h, w, 3) if ch == 3 else (h, w), dtype=dt, device=dev)
+    torch.cuda.synchronize()
+    say(f"frame {w}x{h} ({n} rays), final scene, RT_FLAG_ACCEL_BVH (layer grid), {reps} repetitions after 2 "
+        f"warm-up calls, HIP events; rt_trace all four outputs, rt_aov all six at 1 spp")
+    p = rtow.make_params(w, h, 1, seed=7, flags=FLAGS)
+    ap6 = {k: t.data_ptr() for k, t in aov.items()}
+    t_aov = timed(lambda: ctx.aov_async(cam, p, ap6, s), reps, stream)
+    say(f"rt_aov 1 spp: {t_aov:8.3f} ms")
+    ids = {}
+    for label, sel in order.items():
+        t, ptrs = device_batch(o[sel], d[sel], dev, rtow.TRACE_FIELDS)
+        t_tr = timed(lambda: ctx.trace_async(ptrs, n, FLAGS, s), reps, stream)
+        stream.synchronize()
+        got = t["id"].cpu().numpy()
+        ids[label] = np.empty(n, np.int32)
+        ids[label][sel] = got
+        say(f"rt_trace {label}: {t_tr:8.3f} ms (ratio to rt_aov {t_tr / t_aov:.2f}), "
+            f"{t_tr * 1e6 / n:.3f} ns per ray, hits {int((got >= 0).sum())}, invalid {int((got == -2).sum())}")
+    a_ids, b_ids = ids.values()
+    say(f"ids of the two orders agree: {bool(np.array_equal(a_ids, b_ids))}")
+
+
+def segment_mode(ctx, cam, w, h, reps, dev, stream, say):
+    s = stream.cuda_stream
+    o, d = pixel_centre_rays(cam, w, h)
+    sel = tile_order(w, h)
+    first = ctx.trace(o[sel], d[sel], which=("id", "position", "normal"), flags=FLAGS)
+    hit = first["id"] >= 0
+    so, sd = hemisphere_rays(first["position"][hit], first["normal"][hit], seed=17)
+    n = len(so)
+    ln = np.linalg.norm(sd.astype(np.float64), axis=1)
+    say(f"frame {w}x{h}: {w * h} primary rays, {n} hits, one cosine-hemisphere ray per hit (seed 17); final scene, "
+        f"RT_FLAG_ACCEL_BVH (layer grid), {reps} repetitions after 2 warm-up calls, HIP events, all outputs")
+    out, ptrs = device_batch(so, sd, dev, rtow.SEGMENT_FIELDS)
+    tptrs = {k: v for k, v in ptrs.items() if k != "blocked"}
+
+    def time_trace(label):
+        t = timed(lambda: ctx.trace_async(tptrs, n, FLAGS, s), reps, stream)
+        stream.synchronize()
+        ids = out["id"].cpu().numpy()
+        say(f"rt_trace {label}: {t:8.3f} ms, {t * 1e6 / n:.3f} ns per ray, hits {int((ids >= 0).sum())}")
+        return t, ids
+
+    t_first, ids_trace = time_trace("(first)")
+    rows = []
+    for label, length in [("t_max = +inf", np.inf)] + [(f"length {L:g}", L) for L in LENGTHS]:
+        tm = torch.from_numpy((length / ln).astype(np.float32)).to(dev)
+        ptrs["t_max"] = tm.data_ptr()
+        torch.cuda.synchronize()
+        t = timed(lambda: ctx.segment_async(ptrs, n, FLAGS, s), reps, stream)
+        stream.synchronize()
+        ids, blocked = out["id"].cpu().numpy(), out["blocked"].cpu().numpy()
+        assert ((ids >= 0) == (blocked == 1)).all()
+        rows.append((label, t, int(blocked.sum())))
+        if not np.isfinite(length):
+            say(f"rt_segment {label}: ids equal rt_trace's: {bool(np.array_equal(ids, ids_trace))}")
+    t_last, _ = time_trace("(last)")
+    t_ref = 0.5 * (t_first + t_last)
+    say(f"rt_trace twice: {t_first:.3f} and {t_last:.3f} ms, spread {abs(t_first - t_last):.3f} ms "
+        f"({100 * abs(t_first - t_last) / t_ref:.1f} %): the noise; mean {t_ref:.3f} ms")
+    for label, t, nb in rows:
+        say(f"rt_segment {label}: {t:8.3f} ms, {t / t_ref:.2f} of rt_trace ({t - t_ref:+.3f} ms), "
+            f"blocked {nb} ({100 * nb / n:.1f} %)")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("trace", "segment"), required=True)
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--log", default=None, help="default: profiles/<mode>_pass.log; '' writes none")
+    a = ap.parse_args()
+    log = os.path.join(ROOT, "profiles", f"{a.mode}_pass.log") if a.log is None else a.log
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(device=dev)
+    cam = rtow.camera_cpu(aspect=a.width / a.height, aperture=0.0)
+    with rtow.Context(0) as ctx:
+        ctx.upload(rtow.final_scene())
+        {"trace": trace_mode, "segment": segment_mode}[a.mode](ctx, cam, a.width, a.height, a.reps, dev, stream, say)
+    if log:
+        with open(log, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
