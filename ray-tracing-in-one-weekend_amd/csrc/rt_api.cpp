@@ -416,7 +416,7 @@ void fill_kparams(const rt_context *c, const rt_camera *cam, const rt_params *pr
   kp.tiles_x = (prm->width + rtk::kTile - 1) / rtk::kTile;
   scene_kparams(c->sc, kp);
   grid_kparams(c->sc, kp);
-  kp.seed32 = (uint32_t)prm->seed ^ ((uint32_t)(prm->seed >> 32) * 0x9E3779B9u);
+  kp.seed32 = rt_seed32(prm->seed);
   kp.flags = prm->flags;
   kp.inv_wm1 = (float)(1.0 / (prm->width - 1));
   kp.inv_hm1 = (float)(1.0 / (prm->height - 1));
@@ -587,6 +587,7 @@ int frame_begin(rt_context *c, const rt_camera *cam, const rt_params *prm, hipSt
   rtk::kparams &kp = fs.kp;
   fill_kparams(c, cam, prm, nullptr, kp);
   const scene_state &s = c->sc;
+  fs.n_spheres = (uint32_t)s.dims.n;
   // whether this pass walks the layer grid is decided here alone (fs.grid, fs.placement)
   const bool grid = s.d_grid_cells.p && !(prm->flags & RT_FLAG_LAYER_BVH);
   if (grid && s.fitter && (prm->flags & RT_FLAG_ACCEL_BVH)) {
@@ -613,6 +614,7 @@ int scene_begin(rt_context *c, uint32_t flags, hipStream_t st, rt_frame_setup &f
   scene_kparams(s, kp);
   grid_kparams(s, kp);
   kp.flags = flags;
+  fs.n_spheres = (uint32_t)s.dims.n;
   // refit_grid leaves grid.scale = NaN when a copy into the grid's buffers
   // failed: they hold neither grid until the next grid render refits, and
   // nothing refits here, so the pass walks the layer BVH (the same bits)

@@ -40,7 +40,12 @@ struct rt_frame_setup {
   size_t lds_bytes;       // dynamic LDS of a launch that walks it
   double launch_samples;  // RT_OPT_LAUNCH_SAMPLES
   hipEvent_t ev0, ev1;    // the context's timing events (synchronous callers)
+  uint32_t n_spheres;     // the scene's spheres (rt_bounce checks a ray's `from` against it)
 };
+
+// rt_params.seed as the kernels take it (kparams seed32): the one definition,
+// for the render's arguments (rt_api.cpp fill_kparams) and rt_bounce_rays.seed
+inline uint32_t rt_seed32(uint64_t seed) { return (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x9E3779B9u); }
 
 extern "C" {
 

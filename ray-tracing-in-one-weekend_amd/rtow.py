@@ -41,6 +41,8 @@ ROUTE_LIB_PATH = os.path.join(HERE, "librtow_route.so")
 TRACE_LIB_PATH = os.path.join(HERE, "librtow_trace.so")
 # the same queries within a per-ray distance limit (include/rt_segment.h): a tenth
 SEGMENT_LIB_PATH = os.path.join(HERE, "librtow_segment.so")
+# the render's path step for ray batches (librtow_bounce.so, include/rt_bounce.h)
+BOUNCE_LIB_PATH = os.path.join(HERE, "librtow_bounce.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
@@ -102,6 +104,11 @@ TRACE_MAX_RAYS = 2 ** 31 - 1
 SEGMENT_VERSION = 1  # include/rt_segment.h RT_SEGMENT_VERSION
 # rt_segment_hits' fields in order: "blocked" (uint8), then rt_trace_hits'; the ids are rt_trace's
 SEGMENT_FIELDS = (("blocked", np.uint8, 1),) + TRACE_FIELDS
+BOUNCE_VERSION = 1  # include/rt_bounce.h RT_BOUNCE_VERSION
+BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED, BOUNCE_INVALID = 0, 1, 2, 3  # rt_bounce_out.status
+BOUNCE_FIELDS = ((("status", np.uint8, 1),) + TRACE_FIELDS +
+                 (("scatter", np.float32, 3), ("attenuation", np.float32, 3)))
+BOUNCE_INPUTS = ("origin", "direction", "from", "key")
 SEGMENT_MISS, SEGMENT_INVALID = -1, -2  # RT_SEGMENT_MISS, RT_SEGMENT_INVALID
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
@@ -198,6 +205,18 @@ class SegmentHits(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name, _, _ in SEGMENT_FIELDS]
 
 
+class BounceRays(ctypes.Structure):
+    """rt_bounce_rays: n rays as device (rt_bounce_async) or host (rt_bounce) pointers -- origin, direction
+    (unnormalised), from (the sphere a ray starts on, NULL = none), key (pix, sample, depth) -- and the seed."""
+    _fields_ = ([("n", ctypes.c_uint64)] + [(name, ctypes.c_void_p) for name in ("origin", "direction", "from_", "key")] +
+                [("seed", ctypes.c_uint64)])
+
+
+class BounceOut(ctypes.Structure):
+    """rt_bounce_out: device (rt_bounce_async) or host (rt_bounce) pointers, NULL = not wanted."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in BOUNCE_FIELDS]
+
+
 class DenoiseDesc(ctypes.Structure):
     """rt_denoise_desc: the frame, the options (0 = default) and device
     (rt_denoise_async) or host (rt_denoise) pointers."""
@@ -258,6 +277,7 @@ _guides_lib = None
 _route_lib = None
 _trace_lib = None
 _segment_lib = None
+_bounce_lib = None
 
 
 def _missing(path):
@@ -549,6 +569,22 @@ def segment_lib():
             "rt_segment_async": (None, head + [ctypes.c_void_p]),
             "rt_segment": (None, head + [ctypes.POINTER(ctypes.c_double)])})
     return _segment_lib
+
+
+def bounce_lib():
+    """Load librtow_bounce.so, the render's path step and camera rays for ray
+    batches (raises if it has not been built)."""
+    global _bounce_lib
+    if _bounce_lib is None:
+        head = [ctypes.c_void_p, ctypes.POINTER(BounceRays), ctypes.POINTER(BounceOut), ctypes.c_uint32]
+        cam = [ctypes.c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Params), ctypes.c_int32, ctypes.c_int32,
+               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        _bounce_lib = _load_pass(BOUNCE_LIB_PATH, "rt_bounce_version", BOUNCE_VERSION, {
+            "rt_bounce_async": (None, head + [ctypes.c_void_p]),
+            "rt_bounce": (None, head + [ctypes.POINTER(ctypes.c_double)]),
+            "rt_bounce_camera_rays_async": (None, cam + [ctypes.c_void_p]),
+            "rt_bounce_camera_rays": (None, cam + [ctypes.POINTER(ctypes.c_double)])})
+    return _bounce_lib
 
 
 # the two ray-batch queries, rt_<kind> and rt_<kind>_async: output fields, structures, library
@@ -1009,6 +1045,78 @@ class Context:
         computed."""
         self._ray_batch_async("segment", dev_ptrs, n, flags, stream)
 
+    def bounce(self, origins, directions, keys, seed, from_=None, which=tuple(f[0] for f in BOUNCE_FIELDS), flags=0):
+        """One path step of the render for a batch of rays (rt_bounce,
+        include/rt_bounce.h), synchronously.  origins and directions as in
+        trace(); keys a uint32 (n, 3) array of (pix, sample, depth) per ray;
+        seed the render's (Params.seed); from_ an int32 (n,) array, the sphere
+        each ray starts on (-1 = none), or None for none at all.  The result is
+        a dict of numpy arrays for the names in `which` -- "status" uint8 (n,)
+        (BOUNCE_MISS, _SCATTERED, _ABSORBED, _INVALID), trace()'s four,
+        "scatter" float32 (n, 3) (the next ray's unnormalised direction, from
+        "position") and "attenuation" float32 (n, 3) (the albedo, or on a miss
+        the sky's factor) -- plus "kernel_ms".  flags: a render's interval,
+        metal and acceleration flags."""
+        _reject_unknown(which, [f[0] for f in BOUNCE_FIELDS], "bounce outputs")
+        o = np.ascontiguousarray(origins, np.float32)
+        d = np.ascontiguousarray(directions, np.float32)
+        k = np.ascontiguousarray(keys, np.uint32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape or k.shape != o.shape:
+            raise ValueError(f"origins, directions and keys must all be (n, 3), got {o.shape}, {d.shape} and {k.shape}")
+        n = o.shape[0]
+        rays = BounceRays(n=n, origin=o.ctypes.data, direction=d.ctypes.data, key=k.ctypes.data, seed=int(seed))
+        if from_ is not None:
+            f = np.ascontiguousarray(from_, np.int32)
+            if f.shape != (n,):
+                raise ValueError(f"from_ must be ({n},), got {f.shape}")
+            rays.from_ = f.ctypes.data if n else None
+        out, outs = {}, BounceOut()
+        for field, dt, ch in BOUNCE_FIELDS:
+            if field in which:
+                out[field] = np.zeros((n, 3) if ch == 3 else (n,), dt)
+                setattr(outs, field, out[field].ctypes.data)
+        ms = ctypes.c_double()
+        check(bounce_lib().rt_bounce(self._h, ctypes.byref(rays), ctypes.byref(outs), int(flags), ctypes.byref(ms)),
+              "rt_bounce")
+        out["kernel_ms"] = ms.value
+        return out
+
+    def bounce_async(self, dev_ptrs, n, seed, flags=0, stream=0):
+        """Enqueue the path step (rt_bounce_async) on raw device pointers (e.g.
+        torch tensor.data_ptr() of contiguous tensors): dev_ptrs maps "origin",
+        "direction", "key", optionally "from" and the wanted names of
+        BOUNCE_FIELDS to device pointers; outputs left out are not computed."""
+        outputs = [f[0] for f in BOUNCE_FIELDS]
+        _reject_unknown(dev_ptrs, list(BOUNCE_INPUTS) + outputs, "bounce buffers")
+        missing = [k for k in ("origin", "direction", "key") if k not in dev_ptrs]
+        if missing:
+            raise ValueError(f"bounce_async: {missing} missing")
+        if not 0 <= int(n) <= TRACE_MAX_RAYS:
+            raise ValueError(f"bounce_async: n = {n} is outside 0 .. {TRACE_MAX_RAYS}")
+        rays, outs = BounceRays(n=int(n), seed=int(seed)), BounceOut()
+        for field, ptr in dev_ptrs.items():
+            if field in BOUNCE_INPUTS:
+                setattr(rays, "from_" if field == "from" else field, ptr)
+            else:
+                setattr(outs, field, ptr)
+        check(bounce_lib().rt_bounce_async(self._h, ctypes.byref(rays), ctypes.byref(outs), int(flags),
+                                           ctypes.c_void_p(stream)), "rt_bounce_async")
+
+    def camera_rays(self, cam, params, sample0=0, samples=None):
+        """The render's camera rays of (cam, params) as a batch for bounce()
+        (rt_bounce_camera_rays): samples [sample0, sample0 + samples) of every
+        pixel of the local frame (samples None: params.spp) -> (origins float32
+        (n, 3), directions float32 (n, 3), unnormalised, keys uint32 (n, 3)),
+        ray (lrow * W + col) * samples + j.  A padding row's rays are all-zero
+        and come back BOUNCE_INVALID."""
+        samples = params.spp if samples is None else int(samples)
+        n = max(0, params.local_rows * params.width * samples)
+        o, d, k = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 3), np.uint32)
+        check(bounce_lib().rt_bounce_camera_rays(self._h, ctypes.byref(cam), ctypes.byref(params), int(sample0), samples,
+                                                 o.ctypes.data, d.ctypes.data, k.ctypes.data, None),
+              "rt_bounce_camera_rays")
+        return o, d, k
+
     def visible(self, a, b, shrink=1e-3, flags=0):
         """Whether point b[i] is visible from point a[i]: a bool (n,) array,
         True where no sphere lies on the segment.  a and b are (n, 3) (or one
@@ -1283,6 +1391,35 @@ class Context:
         st = Stats()
         check(lib().rt_collect_stats(self._h, ctypes.byref(st)), "rt_collect_stats")
         return st
+
+
+def path_trace(ctx, cam, params):
+    """rt_render as a wavefront loop over ray batches, the worked example of
+    Context.camera_rays and Context.bounce: bit for bit the render's sums
+    (float32 (local_rows, W, 3)), and the rays traced.  Narrow pixel sums
+    without dither only: spp < 4096 and every albedo <= 1."""
+    opaque = ctx.scene.albedo[np.asarray(ctx.scene.kind) != 2]  # (the render reads a dielectric's albedo as 1)
+    if params.spp >= 4096 or (opaque.size and float(opaque.max()) > 1.0):
+        raise ValueError("path_trace: dithered (spp >= 4096) and wide (an albedo above 1) pixel sums are not restated")
+    f32, npx, spp = np.float32, params.local_rows * params.width, params.spp
+    scale = f32(2.0 ** (31 - max(spp, 1).bit_length() + 1))  # 2^F, F = 31 - floor(log2 spp)
+    sums, traced = np.zeros((npx, 3), np.uint64), 0
+    o, d, key = ctx.camera_rays(cam, params)
+    live = np.nonzero(np.repeat(local_to_global_rows(params) < params.height, params.width * spp))[0]  # no padding rows
+    o, d, key, frm, thr = o[live], d[live], key[live], np.full(live.size, -1, np.int32), np.ones((live.size, 3), f32)
+    for _ in range(params.max_depth):
+        if not live.size:
+            break
+        traced += live.size
+        got = ctx.bounce(o, d, key, params.seed, frm, ("status", "id", "position", "scatter", "attenuation"), params.flags)
+        thr = thr * got["attenuation"]  # the sample's radiance at a miss, the throughput after a hit
+        miss = got["status"] == BOUNCE_MISS
+        np.add.at(sums, live[miss] // spp, np.trunc(thr[miss] * scale).astype(np.uint64))
+        on = got["status"] == BOUNCE_SCATTERED  # compaction: absorbed paths and misses leave
+        key = key[on] + np.array([0, 0, 1], np.uint32)
+        live, o, d, frm, thr = live[on], got["position"][on], got["scatter"][on], got["id"][on], thr[on]
+    image = sums.astype(np.uint32).astype(f32) * (f32(1.0) / scale)  # paths still alive stay black
+    return image.reshape(params.local_rows, params.width, 3), traced
 
 
 def tonemap(sums, spp, mode=RT_TONEMAP_CPU):

@@ -1,4 +1,4 @@
-"""Time the two ray-batch queries (include/rt_trace.h, include/rt_segment.h):
+"""Time the ray-batch passes (include/rt_trace.h, include/rt_segment.h, include/rt_bounce.h):
 final scene, layer grid, everything in device buffers, HIP events around
 repeated enqueues after a warm-up.  There is no target in either mode.
 
@@ -23,8 +23,21 @@ rt_segment is timed without a limit (t_max = +inf: the same walks, one more
 input) and at world lengths 4, 1 and 0.25: the lines say what a limit saves on
 this scene.
 
+bounce: rt_bounce next to rt_trace on the same rays, the final scene's
+secondary rays after one step -- the render's camera rays of the frame
+(rt_bounce_camera_rays, lens camera, 1 spp) pushed through one rt_bounce, the
+scattered ones kept in order.  rt_trace is timed first and last (the noise),
+rt_bounce in between with all seven outputs.  Then the wavefront loop
+(camera rays, max_depth steps with compaction on the device, torch) over
+--loop-width x --loop-height at --loop-spp in chunks of --chunk-spp samples:
+the sum of its rt_bounce and camera-ray kernel times next to rt_render's
+kernel_ms for the same frame.
+
+  python tools/ray_batch_time.py --mode bounce [--width 3840 --height 2160 --reps 20 --log profiles/bounce_pass.log]
+
 Prints the times and writes the same lines to --log."""
 import argparse
+import ctypes
 import os
 import sys
 
@@ -167,9 +180,101 @@ def segment_mode(ctx, cam, w, h, reps, dev, stream, say):
             f"blocked {nb} ({100 * nb / n:.1f} %)")
 
 
+def _tensors(n, fields, dev):
+    return {name: torch.zeros((n, 3) if ch == 3 else (n,), dtype=getattr(torch, np.dtype(dt).name), device=dev)
+            for name, dt, ch in fields}
+
+
+def wavefront_ms(ctx, cam, p, s_lo, s_cnt, dev, stream):
+    """Samples [s_lo, s_lo + s_cnt) of every pixel as a wavefront loop on the
+    device -> (the kernel time of its camera-ray and rt_bounce launches in ms,
+    rays traced).  The pixel sums are not formed: this times the passes."""
+    s = stream.cuda_stream
+    n = p.local_rows * p.width * s_cnt
+    o, d = torch.zeros((n, 3), device=dev), torch.zeros((n, 3), device=dev)
+    key = torch.zeros((n, 3), dtype=torch.int32, device=dev)
+    frm = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * (p.max_depth + 1))]
+    L = rtow.bounce_lib()
+    with torch.cuda.stream(stream):
+        ev[0].record(stream)
+        rtow.check(L.rt_bounce_camera_rays_async(ctx._h, ctypes.byref(cam), ctypes.byref(p), s_lo, s_cnt, o.data_ptr(), d.data_ptr(),
+                                                 key.data_ptr(), s), "rt_bounce_camera_rays_async")
+        ev[1].record(stream)
+        used, traced = 2, 0
+        for _ in range(p.max_depth):
+            n = o.shape[0]
+            if n == 0:
+                break
+            traced += n
+            out = _tensors(n, [f for f in rtow.BOUNCE_FIELDS if f[0] in ("status", "id", "position", "scatter", "attenuation")], dev)
+            ptrs = {k: t.data_ptr() for k, t in out.items()}
+            ptrs.update({"origin": o.data_ptr(), "direction": d.data_ptr(), "key": key.data_ptr(), "from": frm.data_ptr()})
+            ev[used].record(stream)
+            ctx.bounce_async(ptrs, n, p.seed, p.flags, s)
+            ev[used + 1].record(stream)
+            used += 2
+            on = out["status"] == rtow.BOUNCE_SCATTERED
+            o, d, frm = out["position"][on].contiguous(), out["scatter"][on].contiguous(), out["id"][on].contiguous()
+            key = key[on].contiguous()
+            key[:, 2] += 1
+    stream.synchronize()
+    return sum(ev[i].elapsed_time(ev[i + 1]) for i in range(0, used, 2)), traced
+
+
+def bounce_mode(ctx, a, dev, stream, say):
+    w, h, reps, s = a.width, a.height, a.reps, stream.cuda_stream
+    cam = rtow.camera_cpu(aspect=w / h, aperture=0.1)
+    p = rtow.make_params(w, h, 1, seed=7, flags=FLAGS)
+    o, d, key = ctx.camera_rays(cam, p)
+    first = ctx.bounce(o, d, key, p.seed, which=("status", "id", "position", "scatter"), flags=FLAGS)
+    on = first["status"] == rtow.BOUNCE_SCATTERED
+    so, sd, sf = first["position"][on], first["scatter"][on], first["id"][on]
+    sk = key[on] + np.array([0, 0, 1], np.uint32)
+    n = len(so)
+    say(f"frame {w}x{h}: {w * h} camera rays (lens camera, 1 spp, seed 7), {n} scattered after one rt_bounce; final "
+        f"scene, RT_FLAG_ACCEL_BVH (layer grid), {reps} repetitions after 2 warm-up calls, HIP events, all outputs")
+    t, ptrs = device_batch(so, sd, dev, rtow.BOUNCE_FIELDS)
+    t["from"], t["key"] = torch.from_numpy(sf.copy()).to(dev), torch.from_numpy(sk.view(np.int32).copy()).to(dev)
+    ptrs.update({"from": t["from"].data_ptr(), "key": t["key"].data_ptr()})
+    tptrs = {k: ptrs[k] for k in ("origin", "direction", "id", "t", "position", "normal")}
+    torch.cuda.synchronize()
+    t_first = timed(lambda: ctx.trace_async(tptrs, n, FLAGS, s), reps, stream)
+    t_b = timed(lambda: ctx.bounce_async(ptrs, n, p.seed, FLAGS, s), reps, stream)
+    stream.synchronize()
+    st = t["status"].cpu().numpy()
+    t_last = timed(lambda: ctx.trace_async(tptrs, n, FLAGS, s), reps, stream)
+    t_ref = 0.5 * (t_first + t_last)
+    say(f"rt_trace twice: {t_first:.3f} and {t_last:.3f} ms, spread {abs(t_first - t_last):.3f} ms "
+        f"({100 * abs(t_first - t_last) / t_ref:.1f} %): the noise; mean {t_ref:.3f} ms, {n / t_ref / 1e3:.1f} Mray/s")
+    say(f"rt_bounce: {t_b:8.3f} ms, {n / t_b / 1e3:.1f} Mray/s, {t_b / t_ref:.2f} of rt_trace ({t_b - t_ref:+.3f} ms); status "
+        f"miss {int((st == 0).sum())}, scattered {int((st == 1).sum())}, absorbed {int((st == 2).sum())}, "
+        f"invalid {int((st == 3).sum())}")
+    del t
+    # the wavefront loop next to rt_render
+    lw, lh, spp, chunk = a.loop_width, a.loop_height, a.loop_spp, a.chunk_spp
+    cam = rtow.camera_cpu(aspect=lw / lh, aperture=0.1)
+    p = rtow.make_params(lw, lh, spp, seed=7, flags=FLAGS)
+    ctx.render(cam, p)
+    _, stats = ctx.render(cam, p)
+    total, traced = 0.0, 0
+    wavefront_ms(ctx, cam, p, 0, min(chunk, spp), dev, stream)  # warm-up
+    for s_lo in range(0, spp, chunk):
+        ms, tr = wavefront_ms(ctx, cam, p, s_lo, min(chunk, spp - s_lo), dev, stream)
+        total, traced = total + ms, traced + tr
+    say(f"wavefront loop {lw}x{lh} at {spp} spp, max_depth {p.max_depth}, chunks of {chunk} spp: {total:.3f} ms in "
+        f"rt_bounce and camera-ray kernels for {traced} rays ({traced / total / 1e3:.1f} Mray/s); rt_render "
+        f"{stats.kernel_ms:.3f} ms for {stats.segments} segments ({stats.segments / stats.kernel_ms / 1e3:.1f} Mray/s); "
+        f"ratio {total / stats.kernel_ms:.2f}; rays == segments: {traced == stats.segments}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("trace", "segment"), required=True)
+    ap.add_argument("--mode", choices=("trace", "segment", "bounce"), required=True)
+    ap.add_argument("--loop-width", type=int, default=1920)
+    ap.add_argument("--loop-height", type=int, default=1080)
+    ap.add_argument("--loop-spp", type=int, default=100)
+    ap.add_argument("--chunk-spp", type=int, default=4)
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--reps", type=int, default=20)
@@ -187,7 +292,10 @@ def main():
     cam = rtow.camera_cpu(aspect=a.width / a.height, aperture=0.0)
     with rtow.Context(0) as ctx:
         ctx.upload(rtow.final_scene())
-        {"trace": trace_mode, "segment": segment_mode}[a.mode](ctx, cam, a.width, a.height, a.reps, dev, stream, say)
+        if a.mode == "bounce":
+            bounce_mode(ctx, a, dev, stream, say)
+        else:
+            {"trace": trace_mode, "segment": segment_mode}[a.mode](ctx, cam, a.width, a.height, a.reps, dev, stream, say)
     if log:
         with open(log, "w") as f:
             f.write("\n".join(lines) + "\n")
