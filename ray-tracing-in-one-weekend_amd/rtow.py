@@ -43,6 +43,8 @@ TRACE_LIB_PATH = os.path.join(HERE, "librtow_trace.so")
 SEGMENT_LIB_PATH = os.path.join(HERE, "librtow_segment.so")
 # the render's path step for ray batches (librtow_bounce.so, include/rt_bounce.h)
 BOUNCE_LIB_PATH = os.path.join(HERE, "librtow_bounce.so")
+# the wavefront loop's step between two bounces (include/rt_paths.h); RTOW_PATHS_LIB: another build of it, for A/B runs
+PATHS_LIB_PATH = os.environ.get("RTOW_PATHS_LIB") or os.path.join(HERE, "librtow_paths.so")
 
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC = 0, 1, 2
 RT_ERR_INVALID = -1
@@ -109,6 +111,14 @@ BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED, BOUNCE_INVALID = 0, 1, 2, 3  # r
 BOUNCE_FIELDS = ((("status", np.uint8, 1),) + TRACE_FIELDS +
                  (("scatter", np.float32, 3), ("attenuation", np.float32, 3)))
 BOUNCE_INPUTS = ("origin", "direction", "from", "key")
+PATHS_VERSION = 1  # include/rt_paths.h RT_PATHS_VERSION
+# rt_paths_in's arrays and rt_paths_out's next batch: name, dtype, channels
+PATHS_INPUTS = (("status", np.uint8, 1), ("id", np.int32, 1), ("position", np.float32, 3), ("scatter", np.float32, 3),
+                ("attenuation", np.float32, 3), ("key", np.uint32, 3), ("throughput", np.float32, 3),
+                ("slot", np.uint32, 1))
+PATHS_NEXT = (("origin", np.float32, 3), ("direction", np.float32, 3), ("from", np.int32, 1), ("key", np.uint32, 3),
+              ("throughput", np.float32, 3), ("slot", np.uint32, 1))
+PATHS_MAX_SLOTS = (2 ** 32 - 1) // 3
 SEGMENT_MISS, SEGMENT_INVALID = -1, -2  # RT_SEGMENT_MISS, RT_SEGMENT_INVALID
 # rt_context_set_option (include/rt.h): placement / shape / launch options, never semantics
 RT_OPT_GRID_PLACEMENT, RT_OPT_GRID_SCALE, RT_OPT_BVH_LEAF = 1, 2, 3
@@ -217,6 +227,21 @@ class BounceOut(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name, _, _ in BOUNCE_FIELDS]
 
 
+class PathsIn(ctypes.Structure):
+    """rt_paths_in: n rays as device (rt_paths_step_async) or host (rt_paths_step) pointers -- what rt_bounce
+    wrote (status, id, position, scatter, attenuation) and what the rays carried into it (key, throughput, slot)
+    -- the number of pixel sums and the render's shift F."""
+    _fields_ = ([("n", ctypes.c_uint64)] + [(name, ctypes.c_void_p) for name, _, _ in PATHS_INPUTS] +
+                [("n_slots", ctypes.c_uint64), ("shift", ctypes.c_int32), ("reserved", ctypes.c_int32)])
+
+
+class PathsOut(ctypes.Structure):
+    """rt_paths_out: the pixel sums (NULL = no deposit), the next batch (NULL = not wanted) and its count."""
+    _fields_ = ([("sums", ctypes.c_void_p)] +
+                [("from_" if name == "from" else name, ctypes.c_void_p) for name, _, _ in PATHS_NEXT] +
+                [("count", ctypes.c_void_p)])
+
+
 class DenoiseDesc(ctypes.Structure):
     """rt_denoise_desc: the frame, the options (0 = default) and device
     (rt_denoise_async) or host (rt_denoise) pointers."""
@@ -278,6 +303,7 @@ _route_lib = None
 _trace_lib = None
 _segment_lib = None
 _bounce_lib = None
+_paths_lib = None
 
 
 def _missing(path):
@@ -585,6 +611,35 @@ def bounce_lib():
             "rt_bounce_camera_rays_async": (None, cam + [ctypes.c_void_p]),
             "rt_bounce_camera_rays": (None, cam + [ctypes.POINTER(ctypes.c_double)])})
     return _bounce_lib
+
+
+def paths_lib():
+    """Load librtow_paths.so, the wavefront loop's step between two bounces
+    (raises if it has not been built)."""
+    global _paths_lib
+    if _paths_lib is None:
+        step = [ctypes.c_void_p, ctypes.POINTER(PathsIn), ctypes.POINTER(PathsOut)]
+        frame = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p]
+        _paths_lib = _load_pass(PATHS_LIB_PATH, "rt_paths_version", PATHS_VERSION, {
+            "rt_paths_tile": (None, []), "rt_paths_scan_block": (None, []),
+            "rt_paths_shift": (None, [ctypes.c_int32]),
+            "rt_paths_scratch_bytes": (ctypes.c_size_t, [ctypes.c_uint64]),
+            "rt_paths_step_check": (None, [ctypes.POINTER(PathsIn), ctypes.POINTER(PathsOut)]),
+            "rt_paths_step_async": (None, step + [ctypes.c_void_p, ctypes.c_void_p]),
+            "rt_paths_step": (None, step + [ctypes.POINTER(ctypes.c_double)]),
+            "rt_paths_frame_async": (None, frame + [ctypes.c_void_p]),
+            "rt_paths_frame": (None, frame + [ctypes.POINTER(ctypes.c_double)])})
+    return _paths_lib
+
+
+def paths_shift(spp):
+    """rt_paths_shift: the render's F for narrow sums, -1 outside 1 .. 4095."""
+    return paths_lib().rt_paths_shift(int(spp))
+
+
+def paths_scratch_bytes(n):
+    """rt_paths_scratch_bytes: the device scratch of a step over n rays."""
+    return paths_lib().rt_paths_scratch_bytes(int(n))
 
 
 # the two ray-batch queries, rt_<kind> and rt_<kind>_async: output fields, structures, library
@@ -1117,6 +1172,95 @@ class Context:
               "rt_bounce_camera_rays")
         return o, d, k
 
+    def paths_step(self, bounced, keys, throughput, slots, sums, shift,
+                   which=tuple(f[0] for f in PATHS_NEXT)):
+        """The wavefront loop's step after a bounce (rt_paths_step,
+        include/rt_paths.h), synchronously.  bounced: bounce()'s dict with at
+        least "status", "id", "position", "scatter" and "attenuation"; keys
+        uint32 (n, 3), throughput float32 (n, 3) and slots uint32 (n,) what the
+        rays carried into that bounce; sums a C-contiguous uint32 array of 3
+        values per pixel sum that the misses are ADDED into in place, or None
+        for no deposit; shift the render's F (paths_shift).  The result is a
+        dict of the next batch's arrays for the names in `which` ("origin",
+        "direction", "from", "key", "throughput", "slot"), trimmed to the
+        scattered rays in their order, plus "count" and "kernel_ms"."""
+        _reject_unknown(which, [f[0] for f in PATHS_NEXT], "paths outputs")
+        ins = dict(bounced, key=keys, throughput=throughput, slot=slots)
+        missing = [f[0] for f in PATHS_INPUTS if f[0] not in ins]
+        if missing:
+            raise ValueError(f"paths_step: {missing} missing")
+        n = np.asarray(ins["status"]).shape[0]
+        a = PathsIn(n=n, shift=int(shift))
+        keep = []
+        for name, dt, ch in PATHS_INPUTS:
+            v = np.ascontiguousarray(ins[name], dt)
+            if v.shape != ((n, 3) if ch == 3 else (n,)):
+                raise ValueError(f"paths_step: {name} must be {(n, 3) if ch == 3 else (n,)}, got {v.shape}")
+            keep.append(v)
+            setattr(a, name, v.ctypes.data)
+        o = PathsOut()
+        if sums is not None:
+            if (not isinstance(sums, np.ndarray) or sums.dtype != np.uint32 or not sums.flags.c_contiguous or
+                    not sums.flags.writeable or sums.size % 3):
+                raise ValueError("paths_step: sums must be a writeable C-contiguous uint32 array of 3 values per slot")
+            a.n_slots, o.sums = sums.size // 3, sums.ctypes.data
+        out = {}
+        for name, dt, ch in PATHS_NEXT:
+            if name in which:
+                out[name] = np.zeros((n, 3) if ch == 3 else (n,), dt)
+                setattr(o, "from_" if name == "from" else name, out[name].ctypes.data)
+        count, ms = np.zeros(1, np.uint32), ctypes.c_double()
+        o.count = count.ctypes.data
+        check(paths_lib().rt_paths_step(self._h, ctypes.byref(a), ctypes.byref(o), ctypes.byref(ms)), "rt_paths_step")
+        out = {k: v[:int(count[0])] for k, v in out.items()}
+        out["count"], out["kernel_ms"] = int(count[0]), ms.value
+        return out
+
+    def paths_step_async(self, dev_ptrs, n, n_slots, shift, scratch_ptr, stream=0):
+        """Enqueue the step (rt_paths_step_async) on raw device pointers (e.g.
+        torch tensor.data_ptr() of contiguous tensors): dev_ptrs maps the
+        eight names of PATHS_INPUTS and "count" (one uint32) to device
+        pointers, and optionally "sums" and the next batch's arrays as
+        "out_origin", "out_direction", "out_from", "out_key", "out_throughput"
+        and "out_slot"; what is left out is not computed.  scratch_ptr:
+        paths_scratch_bytes(n) bytes, 16-byte aligned."""
+        inputs = [f[0] for f in PATHS_INPUTS]
+        outputs = ["out_" + f[0] for f in PATHS_NEXT]
+        _reject_unknown(dev_ptrs, inputs + outputs + ["sums", "count"], "paths buffers")
+        missing = [k for k in inputs + ["count"] if k not in dev_ptrs]
+        if missing:
+            raise ValueError(f"paths_step_async: {missing} missing")
+        if not 0 <= int(n) <= TRACE_MAX_RAYS:
+            raise ValueError(f"paths_step_async: n = {n} is outside 0 .. {TRACE_MAX_RAYS}")
+        if not 0 <= int(n_slots) <= PATHS_MAX_SLOTS or not 0 <= int(shift) <= 31:
+            raise ValueError(f"paths_step_async: n_slots = {n_slots} or shift = {shift} is out of range")
+        a, o = PathsIn(n=int(n), n_slots=int(n_slots), shift=int(shift)), PathsOut()
+        for name, ptr in dev_ptrs.items():
+            if name in inputs:
+                setattr(a, name, ptr)
+            else:
+                name = name[4:] if name.startswith("out_") else name
+                setattr(o, "from_" if name == "from" else name, ptr)
+        check(paths_lib().rt_paths_step_async(self._h, ctypes.byref(a), ctypes.byref(o), ctypes.c_void_p(scratch_ptr),
+                                              ctypes.c_void_p(stream)), "rt_paths_step_async")
+
+    def paths_frame(self, sums, shift):
+        """The render's final conversion (rt_paths_frame), synchronously: uint32
+        sums of any shape -> float32 (float) sums * 2^-shift of that shape."""
+        s = np.ascontiguousarray(sums, np.uint32)
+        if s.size % 3:
+            raise ValueError("paths_frame: sums must hold 3 values per slot")
+        out = np.zeros(s.shape, np.float32)
+        check(paths_lib().rt_paths_frame(self._h, s.ctypes.data, s.size // 3, int(shift), out.ctypes.data, None),
+              "rt_paths_frame")
+        return out
+
+    def paths_frame_async(self, dev_sums, n_slots, shift, dev_frame, stream=0):
+        """Enqueue the conversion (rt_paths_frame_async) on device pointers: 3 n_slots uint32 -> float32."""
+        check(paths_lib().rt_paths_frame_async(self._h, ctypes.c_void_p(dev_sums), int(n_slots), int(shift),
+                                               ctypes.c_void_p(dev_frame), ctypes.c_void_p(stream)),
+              "rt_paths_frame_async")
+
     def visible(self, a, b, shrink=1e-3, flags=0):
         """Whether point b[i] is visible from point a[i]: a bool (n,) array,
         True where no sphere lies on the segment.  a and b are (n, 3) (or one
@@ -1419,6 +1563,90 @@ def path_trace(ctx, cam, params):
         key = key[on] + np.array([0, 0, 1], np.uint32)
         live, o, d, frm, thr = live[on], got["position"][on], got["scatter"][on], got["id"][on], thr[on]
     image = sums.astype(np.uint32).astype(f32) * (f32(1.0) / scale)  # paths still alive stay black
+    return image.reshape(params.local_rows, params.width, 3), traced
+
+
+def _narrow_sums_only(ctx, params, who):
+    opaque = ctx.scene.albedo[np.asarray(ctx.scene.kind) != 2]  # (the render reads a dielectric's albedo as 1)
+    if params.spp >= 4096 or (opaque.size and float(opaque.max()) > 1.0):
+        raise ValueError(f"{who}: dithered (spp >= 4096) and wide (an albedo above 1) pixel sums are not restated")
+
+
+def path_trace_device(ctx, cam, params, chunk_spp=4, stream=None):
+    """path_trace's loop on the device (the worked example of
+    Context.paths_step_async): camera rays per chunk of chunk_spp samples, then
+    max_depth rounds of rt_bounce and rt_paths_step with key, throughput and
+    slot ping-ponged, and rt_paths_frame at the end.  Only each step's count (4
+    bytes) crosses to the host.  -> (float32 (local_rows, W, 3), bit for bit
+    the render's sums, and the rays traced).  A padding row's rays are the
+    camera batch's all-zero ones: rt_bounce reports them INVALID and the step
+    drops them.  stream: a torch.cuda.Stream of the caller's (not torch's
+    default stream, whose handle 0 means "the context's own" to the passes);
+    None: a stream of the loop's own, which waits for torch's current one."""
+    import torch
+    _narrow_sums_only(ctx, params, "path_trace_device")
+    if int(chunk_spp) < 1:
+        raise ValueError(f"path_trace_device: chunk_spp = {chunk_spp} must be at least 1")
+    npx, spp, shift = params.local_rows * params.width, params.spp, 31 - max(params.spp, 1).bit_length() + 1
+    dev = torch.device("cuda", ctx.device)
+    if stream is None:
+        stream = torch.cuda.Stream(device=dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    elif stream.cuda_stream == 0:
+        raise ValueError("path_trace_device: torch's default stream is not a stream of the caller's own")
+    s, traced = stream.cuda_stream, 0
+    valid_px = int((local_to_global_rows(params) < params.height).sum()) * params.width
+    with torch.cuda.stream(stream):
+        sums = torch.zeros((max(npx, 1), 3), dtype=torch.int32, device=dev)
+        frame = torch.zeros((max(npx, 1), 3), dtype=torch.float32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        bufs = {}  # per chunk size (the last chunk may be shorter)
+        for s_lo in range(0, spp, int(chunk_spp)):
+            cnt = min(int(chunk_spp), spp - s_lo)
+            n = npx * cnt
+            if n == 0:
+                break
+            if cnt not in bufs:
+                f3 = lambda: torch.empty((n, 3), dtype=torch.float32, device=dev)  # noqa: E731
+                i1 = lambda: torch.empty((n,), dtype=torch.int32, device=dev)  # noqa: E731
+                b = {"origin": f3(), "direction": f3(), "from": i1(), "status": torch.empty((n,), dtype=torch.uint8, device=dev),
+                     "id": i1(), "position": f3(), "scatter": f3(), "attenuation": f3(),
+                     "key": [torch.empty((n, 3), dtype=torch.int32, device=dev) for _ in range(2)],
+                     "throughput": [f3(), f3()], "slot": [i1(), i1()],
+                     "slot0": torch.arange(n, dtype=torch.int32, device=dev) // cnt,
+                     "scratch": torch.empty(paths_scratch_bytes(n), dtype=torch.uint8, device=dev)}
+                bufs[cnt] = b
+            b = bufs[cnt]
+            check(bounce_lib().rt_bounce_camera_rays_async(ctx._h, ctypes.byref(cam), ctypes.byref(params), s_lo, cnt,
+                                                           b["origin"].data_ptr(), b["direction"].data_ptr(),
+                                                           b["key"][0].data_ptr(), s), "rt_bounce_camera_rays_async")
+            b["from"].fill_(-1)
+            b["throughput"][0].fill_(1.0)
+            b["slot"][0].copy_(b["slot0"])
+            live, pad = n, n - valid_px * cnt  # (the padding rows' rays leave in the first step, untraced)
+            for depth in range(params.max_depth):
+                if live == 0:
+                    break
+                traced += live - (pad if depth == 0 else 0)
+                i, o = depth & 1, (depth + 1) & 1
+                ctx.bounce_async({"origin": b["origin"].data_ptr(), "direction": b["direction"].data_ptr(),
+                                  "from": b["from"].data_ptr(), "key": b["key"][i].data_ptr(),
+                                  "status": b["status"].data_ptr(), "id": b["id"].data_ptr(),
+                                  "position": b["position"].data_ptr(), "scatter": b["scatter"].data_ptr(),
+                                  "attenuation": b["attenuation"].data_ptr()}, live, params.seed, params.flags, s)
+                ctx.paths_step_async({"status": b["status"].data_ptr(), "id": b["id"].data_ptr(),
+                                      "position": b["position"].data_ptr(), "scatter": b["scatter"].data_ptr(),
+                                      "attenuation": b["attenuation"].data_ptr(), "key": b["key"][i].data_ptr(),
+                                      "throughput": b["throughput"][i].data_ptr(), "slot": b["slot"][i].data_ptr(),
+                                      "sums": sums.data_ptr(), "count": count.data_ptr(),
+                                      "out_origin": b["origin"].data_ptr(), "out_direction": b["direction"].data_ptr(),
+                                      "out_from": b["from"].data_ptr(), "out_key": b["key"][o].data_ptr(),
+                                      "out_throughput": b["throughput"][o].data_ptr(), "out_slot": b["slot"][o].data_ptr()},
+                                     live, npx, shift, b["scratch"].data_ptr(), s)
+                live = int(count.item())  # the 4 bytes
+        if npx:
+            ctx.paths_frame_async(sums.data_ptr(), npx, shift, frame.data_ptr(), s)
+        image = frame[:npx].cpu().numpy()
     return image.reshape(params.local_rows, params.width, 3), traced
 
 

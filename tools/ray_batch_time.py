@@ -35,6 +35,17 @@ kernel_ms for the same frame.
 
   python tools/ray_batch_time.py --mode bounce [--width 3840 --height 2160 --reps 20 --log profiles/bounce_pass.log]
 
+paths: the wavefront loop's glue between two bounces (include/rt_paths.h) over
+--loop-width x --loop-height at --loop-spp in chunks of --chunk-spp samples,
+three ways in one run, each twice (the spread is the run's noise): (a) the
+loop as --mode bounce runs it, torch boolean indexing and no pixel sums; (b)
+that loop with the sums formed by torch (index_add_ on int64), so that it does
+the same work -- the comparison point; (c) rt_paths_step, rtow.path_trace_device's
+sequence.  HIP events around the whole loop (host waits included) and around
+every launch sequence; rt_render's kernel_ms for the same segments next to them.
+
+  python tools/ray_batch_time.py --mode paths [--log profiles/paths_pass.log]
+
 Prints the times and writes the same lines to --log."""
 import argparse
 import ctypes
@@ -185,12 +196,18 @@ def _tensors(n, fields, dev):
             for name, dt, ch in fields}
 
 
-def wavefront_ms(ctx, cam, p, s_lo, s_cnt, dev, stream):
+def wavefront_ms(ctx, cam, p, s_lo, s_cnt, dev, stream, sums=None):
     """Samples [s_lo, s_lo + s_cnt) of every pixel as a wavefront loop on the
     device -> (the kernel time of its camera-ray and rt_bounce launches in ms,
-    rays traced).  The pixel sums are not formed: this times the passes."""
+    rays traced).  The pixel sums are not formed: this times the passes.  With
+    sums (int64 (pixels, 3)) torch forms them too: throughput, clamp, index_add_."""
     s = stream.cuda_stream
     n = p.local_rows * p.width * s_cnt
+    if sums is not None:
+        scale = float(2 ** rtow.paths_shift(p.spp))
+        with torch.cuda.stream(stream):
+            thr = torch.ones((n, 3), device=dev)
+            slot = torch.arange(n, device=dev) // s_cnt
     o, d = torch.zeros((n, 3), device=dev), torch.zeros((n, 3), device=dev)
     key = torch.zeros((n, 3), dtype=torch.int32, device=dev)
     frm = torch.full((n,), -1, dtype=torch.int32, device=dev)
@@ -215,6 +232,11 @@ def wavefront_ms(ctx, cam, p, s_lo, s_cnt, dev, stream):
             ev[used + 1].record(stream)
             used += 2
             on = out["status"] == rtow.BOUNCE_SCATTERED
+            if sums is not None:
+                thr = thr * out["attenuation"]
+                miss = out["status"] == rtow.BOUNCE_MISS
+                sums.index_add_(0, slot[miss], torch.clamp(thr[miss] * scale, 0.0, 4294967040.0).to(torch.int64))
+                thr, slot = thr[on].contiguous(), slot[on].contiguous()
             o, d, frm = out["position"][on].contiguous(), out["scatter"][on].contiguous(), out["id"][on].contiguous()
             key = key[on].contiguous()
             key[:, 2] += 1
@@ -268,9 +290,116 @@ def bounce_mode(ctx, a, dev, stream, say):
         f"ratio {total / stats.kernel_ms:.2f}; rays == segments: {traced == stats.segments}")
 
 
+def paths_loop_ms(ctx, cam, p, chunk, dev, stream):
+    """rtow.path_trace_device's sequence with events around every launch
+    sequence -> (ms in camera-ray and rt_bounce kernels, ms in the step's three
+    kernels, rays traced, the frame)."""
+    s, npx, spp, shift = stream.cuda_stream, p.local_rows * p.width, p.spp, rtow.paths_shift(p.spp)
+    pairs = {"bounce": [], "step": []}
+
+    def timed_call(kind, fn):
+        e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        e[0].record(stream)
+        fn()
+        e[1].record(stream)
+        pairs[kind].append(e)
+
+    L, traced = rtow.bounce_lib(), 0
+    with torch.cuda.stream(stream):
+        n = npx * chunk
+        f3 = lambda: torch.empty((n, 3), device=dev)  # noqa: E731
+        i1 = lambda: torch.empty((n,), dtype=torch.int32, device=dev)  # noqa: E731
+        t = {k: f3() for k in ("origin", "direction", "position", "scatter", "attenuation")}
+        t.update({"from": i1(), "id": i1(), "status": torch.empty((n,), dtype=torch.uint8, device=dev)})
+        key, thr, slot = [torch.empty((n, 3), dtype=torch.int32, device=dev) for _ in range(2)], [f3(), f3()], [i1(), i1()]
+        scratch = torch.empty(rtow.paths_scratch_bytes(n), dtype=torch.uint8, device=dev)
+        sums = torch.zeros((npx, 3), dtype=torch.int32, device=dev)
+        frame, count = torch.zeros((npx, 3), device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+        for s_lo in range(0, spp, chunk):
+            cnt = min(chunk, spp - s_lo)
+            live = npx * cnt
+            timed_call("bounce", lambda: rtow.check(L.rt_bounce_camera_rays_async(
+                ctx._h, ctypes.byref(cam), ctypes.byref(p), s_lo, cnt, t["origin"].data_ptr(), t["direction"].data_ptr(),
+                key[0].data_ptr(), s), "rt_bounce_camera_rays_async"))
+            t["from"].fill_(-1)
+            thr[0].fill_(1.0)
+            slot[0][:live] = torch.arange(live, dtype=torch.int32, device=dev) // cnt
+            for depth in range(p.max_depth):
+                if live == 0:
+                    break
+                traced += live
+                i, o = depth & 1, (depth + 1) & 1
+                ptrs = {k: t[k].data_ptr() for k in ("origin", "direction", "from", "status", "id", "position", "scatter",
+                                                     "attenuation")}
+                timed_call("bounce", lambda: ctx.bounce_async(dict(ptrs, key=key[i].data_ptr()), live, p.seed, p.flags, s))
+                step = {k: t[k].data_ptr() for k in ("status", "id", "position", "scatter", "attenuation")}
+                step.update(key=key[i].data_ptr(), throughput=thr[i].data_ptr(), slot=slot[i].data_ptr(),
+                            sums=sums.data_ptr(), count=count.data_ptr(), out_origin=t["origin"].data_ptr(),
+                            out_direction=t["direction"].data_ptr(), out_from=t["from"].data_ptr(),
+                            out_key=key[o].data_ptr(), out_throughput=thr[o].data_ptr(), out_slot=slot[o].data_ptr())
+                timed_call("step", lambda: ctx.paths_step_async(step, live, npx, shift, scratch.data_ptr(), s))
+                live = int(count.item())
+        ctx.paths_frame_async(sums.data_ptr(), npx, shift, frame.data_ptr(), s)
+        image = frame.cpu().numpy()
+    ms = {k: sum(a.elapsed_time(b) for a, b in v) for k, v in pairs.items()}
+    return ms["bounce"], ms["step"], traced, image.reshape(p.local_rows, p.width, 3)
+
+
+def paths_mode(ctx, a, dev, stream, say):
+    lw, lh, spp, chunk = a.loop_width, a.loop_height, a.loop_spp, a.chunk_spp
+    cam = rtow.camera_cpu(aspect=lw / lh, aperture=0.1)
+    p = rtow.make_params(lw, lh, spp, seed=7, flags=FLAGS)
+    ctx.render(cam, p)
+    img, stats = ctx.render(cam, p)
+    shift = rtow.paths_shift(spp)
+    say(f"frame {lw}x{lh} at {spp} spp, max_depth {p.max_depth}, chunks of {chunk} spp, final scene, lens camera, seed 7, "
+        f"RT_FLAG_ACCEL_BVH (layer grid); librtow_paths {rtow.device_code_sha16(rtow.PATHS_LIB_PATH)} "
+        f"({os.path.relpath(rtow.PATHS_LIB_PATH, ROOT)}), tile {rtow.paths_lib().rt_paths_tile()}, scan block "
+        f"{rtow.paths_lib().rt_paths_scan_block()}")
+    say(f"rt_render: {stats.kernel_ms:.3f} ms for {stats.segments} segments ({stats.segments / stats.kernel_ms / 1e3:.1f} Mray/s)")
+
+    def whole(fn):
+        stream.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        got = fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1), got
+
+    def torch_loop(with_sums):
+        sums = torch.zeros((lw * lh, 3), dtype=torch.int64, device=dev) if with_sums else None
+        total, traced = 0.0, 0
+        for s_lo in range(0, spp, chunk):
+            ms, tr = wavefront_ms(ctx, cam, p, s_lo, min(chunk, spp - s_lo), dev, stream, sums)
+            total, traced = total + ms, traced + tr
+        image = None
+        if with_sums:
+            with torch.cuda.stream(stream):
+                image = ((sums & 0xFFFFFFFF).to(torch.float32) * (1.0 / 2 ** shift)).cpu().numpy().reshape(lh, lw, 3)
+        return total, None, traced, image
+
+    runs = {"(a) torch indexing, no sums": lambda: torch_loop(False), "(b) torch indexing + index_add_ sums": lambda: torch_loop(True),
+            "(c) rt_paths_step": lambda: paths_loop_ms(ctx, cam, p, chunk, dev, stream)}
+    small = rtow.make_params(lw, lh, min(chunk, spp), seed=7, flags=FLAGS)
+    wavefront_ms(ctx, cam, small, 0, small.spp, dev, stream, torch.zeros((lw * lh, 3), dtype=torch.int64, device=dev))  # warm-up
+    paths_loop_ms(ctx, cam, small, small.spp, dev, stream)
+    for rnd in ("first", "second"):
+        for label, fn in runs.items():
+            ms, (bounce, step, traced, image) = whole(fn)
+            same = "" if image is None else f"; frame == rt_render's: {image.tobytes() == img.tobytes()}"
+            steps = "" if step is None else f", {step:.3f} ms in the step's three kernels"
+            say(f"{label} ({rnd}): whole loop {ms:.3f} ms (events, host waits included), {bounce:.3f} ms in rt_bounce and "
+                f"camera-ray kernels{steps}; {traced} rays (== segments: {traced == stats.segments}); whole loop / rt_render "
+                f"{ms / stats.kernel_ms:.2f}{same}")
+    ms, (image, traced) = whole(lambda: rtow.path_trace_device(ctx, cam, p, chunk, stream))
+    say(f"rtow.path_trace_device (no per-launch events): whole loop {ms:.3f} ms; frame == rt_render's: "
+        f"{image.tobytes() == img.tobytes()}; rays == segments: {traced == stats.segments}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("trace", "segment", "bounce"), required=True)
+    ap.add_argument("--mode", choices=("trace", "segment", "bounce", "paths"), required=True)
     ap.add_argument("--loop-width", type=int, default=1920)
     ap.add_argument("--loop-height", type=int, default=1080)
     ap.add_argument("--loop-spp", type=int, default=100)
@@ -294,6 +423,8 @@ def main():
         ctx.upload(rtow.final_scene())
         if a.mode == "bounce":
             bounce_mode(ctx, a, dev, stream, say)
+        elif a.mode == "paths":
+            paths_mode(ctx, a, dev, stream, say)
         else:
             {"trace": trace_mode, "segment": segment_mode}[a.mode](ctx, cam, a.width, a.height, a.reps, dev, stream, say)
     if log:
